@@ -10,8 +10,14 @@ the weak-scaling run (every rank one 1 M slab of a channel N times as long) goes
 
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (k_substep): algorithmic bytes
 per launch (284 + 52*K_half bytes per particle-substep) / its mean duration from HIP
-events on the engine's own stream.  `cpu_baseline` times the CPU oracle (a port of the reference's
-algorithm; the reference itself needs LAMMPS + OpenFOAM, absent here) on a bounded sample.
+events on the engine's own stream.
+
+A plain run times the headline only: set-up, W warm-up steps, K timed steps, the line.  --full adds every side
+measurement: `cpu_baseline` (the CPU oracle, a port of the reference's algorithm -- the reference itself needs
+LAMMPS + OpenFOAM, absent here -- on a bounded sample) with the GPU-vs-oracle `parity` of the final state, the coupled
+CFD-DEM steps and the host boundary, `fluidised_bed`, the `configs` C2 / C3 / C5 with `roofline.frac_2m`, and at N > 1
+`weak_scaling`.  --dump-outputs DIR writes what the timed path computed in its last step (the owned atoms' x, v,
+omega, f, torque and tag, sorted by tag; a fixed sample of DUMP_SAMPLE atoms of larger beds) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -26,6 +32,8 @@ import numpy as np  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8 TB/s peak
 PMC_SUMMARIES = ("r06_pmc_summary.json", "r05_pmc_summary.json", "r04_pmc_summary.json")   # committed PMC passes, newest first (tests/profile_round.sh)
+DUMP_SAMPLE = 262144    # --dump-outputs: atoms kept of a larger bed (6 float64 arrays: 34 MB), chosen with DUMP_SEED
+DUMP_SEED = 20240607
 
 
 def build_engine(bed, script):
@@ -345,6 +353,19 @@ def config_cpu_leg(bed, cfg, substeps):
                       "thread" % (bed["n"], substeps, secs)}
 
 
+DUMP_ARRAYS = ("tag", "x", "v", "omega", "f", "torque")
+
+
+def dump_outputs(outdir, state):
+    """--dump-outputs: the state the timed steps left (sorted by tag) as outdir/<name>.npy, float64; of a bed larger than
+    DUMP_SAMPLE atoms the same seeded sample of positions in tag order every run"""
+    n = len(state["tag"])
+    keep = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False)) if n > DUMP_SAMPLE else slice(None)
+    os.makedirs(outdir, exist_ok=True)
+    for name in DUMP_ARRAYS:
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(state[name][keep], dtype=np.float64))
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--cpu-worker":
         return cpu_worker(sys.argv[2:])
@@ -369,7 +390,8 @@ def main():
     ap.add_argument("--scaling", choices=["both", "weak", "strong"], default="both",
                     help="N > 1: strong = --particles in total, split into N domains (BASELINE config C4: the `value` of "
                          "the JSON line); weak = every rank owns one --particles slab (`value` only with --scaling weak); "
-                         "both (default) = strong as `value`, weak next to it as `weak_scaling`.  N = 1: identical")
+                         "both (default) = strong as `value`, with --full weak next to it as `weak_scaling`.  N = 1: "
+                         "identical")
     ap.add_argument("--decomposition", choices=["auto", "slabs", "bricks"], default="auto",
                     help="N > 1, strong scaling: x-slabs, or bricks of a 3-D processor grid (sedifoam_amd.halo.brick_grid: "
                          "periodic dimensions first, as cubic as N allows: 8 -> 4x1x2, 4 -> 2x1x2 on the channel bed); "
@@ -397,7 +419,17 @@ def main():
     ap.add_argument("--watchdog", type=float, default=None,
                     help="N > 1: seconds after which a rank that is still running ends the job with rc 124 (a collective "
                          "that never completes must not hold the node forever; default 1500, 0 = off)")
+    ap.add_argument("--full", action="store_true",
+                    help="also every side measurement (CPU baselines and the GPU-vs-oracle parity, coupled steps and the "
+                         "host boundary, fluidised_bed, configs C2 / C3 / C5 and roofline.frac_2m, N > 1: weak_scaling); "
+                         "the --no-* options above drop single ones of them.  Without it the run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed (x, v, omega, f, torque, tag of the owned atoms, "
+                         "sorted by tag; a fixed sample of %d atoms of a larger bed) as DIR/<name>.npy, float64"
+                         % DUMP_SAMPLE)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -731,7 +763,7 @@ def main():
         lmp = make_driver("from_bed", bed)
         elapsed, n_total, launches, kernel_ms, info, _info_after = timed_run(lmp)
         main_exchange_us, main_rebuild_ms = exchange_us[0], rebuild_ms[0]
-    elif world > 1 and args.scaling == "both":
+    elif world > 1 and args.scaling == "both" and args.full:
         try:
             wdrv = make_driver("from_bed", bed)
             el_w, n_w, l_w, k_w, i_w, _ia = timed_run(wdrv)
@@ -752,6 +784,20 @@ def main():
     elif world == 1:
         lmp = build_engine(bed, script)
         elapsed, n_total, launches, kernel_ms, info, _info_after = timed_run(lmp)
+    if args.dump_outputs:
+        # (before anything below steps the same engine again; at N > 1 the domains gathered on rank 0)
+        STAGE[0] = "--dump-outputs"
+        st = (lmp.e.lmp if hasattr(lmp, "e") else lmp).get_state()
+        if dist is not None and world > 1:
+            parts = [None] * world if rank == 0 else None
+            dist.gather_object({k: st[k] for k in DUMP_ARRAYS}, parts, dst=0)
+            if rank == 0:
+                st = {k: np.concatenate([q[k] for q in parts]) for k in DUMP_ARRAYS}
+                o = np.argsort(st["tag"], kind="stable")
+                st = {k: a[o] for k, a in st.items()}
+        if rank == 0:
+            dump_outputs(args.dump_outputs, st)
+        del st
     is_strong = world > 1 and args.scaling != "weak"
     k_half = info.npairs_full / 2.0 / max(info.nlocal, 1)
 
@@ -842,7 +888,7 @@ def main():
             break
     # secondary metric of BASELINE.json: coupled CFD-DEM steps/s (drag closure + drag assembly + S sub-steps +
     # cell owner + void-fraction / Ue scatter + Asrc) through the device-resident enhancedCloud, frozen fluid
-    if world == 1 and not args.slab_driver and not args.no_coupled:
+    if world == 1 and not args.slab_driver and args.full and not args.no_coupled:
         from sedifoam_amd import enhancedCloud
         # cells at least 3 d wide (a centre-counted void fraction above 1 makes every closure return inf)
         mesh_n = np.clip(((bed["boxhi"] - bed["boxlo"]) / 3.0e-3).astype(int), 1, 32)
@@ -936,7 +982,7 @@ def main():
     # N = 1: the loose disordered ("fluidised") bed of the same size next to the headline -- BASELINE config C3 is a
     # fluidised bed; the lattice of the headline is the best case (every listed neighbour touches, a rebuild every ~170
     # sub-steps).  Same engine path, same timing rules, shorter run.
-    if world == 1 and not args.slab_driver and not args.no_fluidised and args.bed == "packed" and not bed_kw:
+    if world == 1 and not args.slab_driver and args.full and not args.no_fluidised and args.bed == "packed" and not bed_kw:
         fbed = synthetic.fcc_bed(ncells, seed=12345 + 3, **FLUIDISED)
         flmp = build_engine(fbed, synthetic.hertz_script(fbed, **kw))
         keep = (args.steps, args.warmup)
@@ -962,7 +1008,7 @@ def main():
     # single-GPU configurations -- C2 (10 k grains, 32^3 mesh), C3 (100 k fluidised), C5 (500 k polydisperse + cohesive +
     # lubricate/poly) -- each through the same engine path and timing rules, with its coupled step where it has a mesh
     cfg_cases = None
-    if (world == 1 and not args.slab_driver and not args.no_configs and args.bed == "packed" and not bed_kw
+    if (world == 1 and not args.slab_driver and args.full and not args.no_configs and args.bed == "packed" and not bed_kw
             and args.particles == 1000000):
         keep = (args.steps, args.warmup)
         b2 = synthetic.fcc_bed(synthetic.fcc_cells_for(2000000), seed=12345 + 3)
@@ -1046,7 +1092,7 @@ def main():
         }.get(direct_on, "one grouped ncclSend/ncclRecv per sub-step + unpack kernel")
         if halo_note:
             out["config"]["halo_note"] = halo_note
-    if rank == 0 and not args.no_cpu_baseline:   # (on rank 0's host cores; at N > 1 the other ranks are done)
+    if rank == 0 and args.full and not args.no_cpu_baseline:   # (on rank 0's host cores; at N > 1 the other ranks are done)
         sample_n = args.cpu_sample or 1000000
         sub = 50
         do_parity = (world == 1 and not args.no_parity and not args.slab_driver and sample_n == args.particles and not bed_kw)

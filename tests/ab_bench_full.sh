@@ -3,7 +3,7 @@
 for v in "$@"; do
   p=""; [ "$v" != "default" ] && p=$GRAFT_REPO_ROOT/sedifoam_amd/libsedifoam_amd_$v.so
   echo "== $v"
-  SF_LIB_PATH=$p python bench.py --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
+  SF_LIB_PATH=$p python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
 import json, sys
 d = json.loads(sys.stdin.readline())
 r = d['roofline']

@@ -9,5 +9,5 @@ root=$GRAFT_REPO_ROOT
 for w in $ranks; do
   echo "== $w ranks on one GPU, $n particles"
   SF_RCCL_LIB=/tmp/libstandin_rccl.so timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $w --master-addr 127.0.0.1 --master-port $((29700 + w)) \
-    $root/bench.py --gpus $w --one-gpu --particles $n --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-profile "$@" 2>&1 | grep -v "^W0\|^\*\*\*\|OMP_NUM" | tail -3 | cut -c1-1500
+    $root/bench.py --gpus $w --one-gpu --full --particles $n --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-profile "$@" 2>&1 | grep -v "^W0\|^\*\*\*\|OMP_NUM" | tail -3 | cut -c1-1500
 done
