@@ -392,6 +392,11 @@ int sfk_cell_owner(int n, const double *x, const double origin[3], const double 
  * uniform along k (origin/dx) */
 int sfk_cell_owner_graded(int n, const double *x, const double origin[3], const double dx[3],
                           const int ncell[3], const double *const dev_faces[3], int *cell, void *stream);
+/* the device formatter of `dump custom` (sf_dump.hip) on HOST arrays: "%d\n" of every ints[k], then "%g\n" of every
+ * values[k], byte-identical to glibc printf, into out (cap bytes); *nbytes = the byte count (also when it does not fit,
+ * which is an error).  At most 12 bytes per int and 14 per double. */
+int sfk_dump_format(const double *values, long long nvalues, const int *ints, long long nints, char *out,
+                    long long cap, long long *nbytes);
 
 /* ------------------------------------------------------------------------------------------
  * (3) enhancedCloud surface -- lammpsFoam/enhancedCloud.H:183-249, enhancedCloud.C

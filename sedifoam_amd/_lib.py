@@ -194,6 +194,7 @@ _SIGS = {
     "sfk_drag_model_jd": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, C.c_double, C.c_double, vp, vp]),
     "sfk_cell_owner": (C.c_int, [C.c_int, vp, dp, dp, ip, vp, vp]),
     "sfk_cell_owner_graded": (C.c_int, [C.c_int, vp, dp, dp, ip, C.POINTER(C.c_void_p), vp, vp]),
+    "sfk_dump_format": (C.c_int, [vp, C.c_longlong, vp, C.c_longlong, vp, C.c_longlong, C.POINTER(C.c_longlong)]),
     "sf_cloud_create": (C.c_int, [vp, C.POINTER(CloudMesh), C.POINTER(CloudProps), C.c_double, C.POINTER(vp)]),
     "sf_cloud_destroy": (C.c_int, [vp]),
     "sf_cloud_set_fluid": (C.c_int, [vp, dp, dp, dp, dp]),

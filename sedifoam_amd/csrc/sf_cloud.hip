@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/sedifoam_amd.h"
+#include "sf_dump.h"
 #include "sf_handles.h"
 #include "sf_roctx.h"
 #include "sf_smooth.h"
@@ -725,7 +726,7 @@ class Cloud {
       t1 = now();
       {
         Range r("lammps");
-        e.run(subSteps_);  // lammpsEvolveForward without the host round trip
+        run_steps(*lmp_, subSteps_);  // lammpsEvolveForward without the host round trip (and the dump frames)
         t_.lammps += sync_now() - t1;
       }
       // Cloud::move: the new cell owner is recomputed from the DEM positions wherever it is used

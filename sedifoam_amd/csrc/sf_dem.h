@@ -561,6 +561,7 @@ class DemEngine {
   double* d_vOld() const { return vOld_.as<double>(); }
   int* d_tag() const { return tag_.as<int>(); }
   int* d_type() const { return type_.as<int>(); }
+  int* d_mask() const { return mask_.as<int>(); }   // group bits ([3P] atom->mask)
   int* d_foamCpuId() const { return foamCpuId_.as<int>(); }
   int max_tag() const { return max_tag_; }
 

@@ -19,6 +19,7 @@
 #include <array>
 
 #include "../../include/sedifoam_amd.h"
+#include "sf_dump.h"
 #include "sf_handles.h"
 #include "sf_roctx.h"
 
@@ -1566,6 +1567,53 @@ static SfLammps* H(void* p)
 {
   if (!p) sf::fail("null engine handle");
   return static_cast<SfLammps*>(p);
+}
+
+// the single file of a dump on a decomposed run ([3P] Dump::write: the procs send their buffers to proc 0, which writes
+// them in rank order): the block sizes first (an all-reduce of every rank's byte and atom count), then one grouped
+// receive per rank on rank 0 into *dst after its own block, one send on every other rank
+size_t sf::dump_gather(SfLammps& L, const char* src, size_t nbytes, unsigned long long count, char** dst, size_t* cap,
+                       unsigned long long* count_total)
+{
+  auto* hc = static_cast<HaloComm*>(L.halo);
+  if (!hc || !hc->comm) fail("dump: a single file on %d ranks needs the engine's communicator (the bricks of read_data)",
+                             L.world_size);
+  const int W = hc->world, r = hc->rank;
+  std::vector<double> sz(2 * (size_t)W, 0.0);
+  sz[2 * r] = (double)nbytes;   // (exact below 2^53 bytes)
+  sz[2 * r + 1] = (double)count;
+  if (sf_slab_allreduce_sum(&L, sz.data(), 2 * W) != 0) fail("%s", last_error().c_str());
+  size_t total = 0;
+  unsigned long long atoms = 0;
+  for (int k = 0; k < W; k++) {
+    total += (size_t)sz[2 * k];
+    atoms += (unsigned long long)sz[2 * k + 1];
+  }
+  *count_total = atoms;
+  hipStream_t st = L.eng.stream();
+  RcclApi& a = rccl();
+  if (r == 0) {
+    if (total + 1 > *cap) {
+      SF_HIP(hipStreamSynchronize(st));
+      if (*dst) SF_HIP(hipFree(*dst));
+      *cap = total + total / 4 + 4096;
+      SF_HIP(hipMalloc(reinterpret_cast<void**>(dst), *cap));
+    }
+    if (nbytes) SF_HIP(hipMemcpyAsync(*dst, src, nbytes, hipMemcpyDeviceToDevice, st));
+    size_t off = nbytes;
+    SF_NCCL(a.GroupStart());
+    for (int k = 1; k < W; k++) {
+      const size_t nk = (size_t)sz[2 * k];
+      if (nk) SF_NCCL(a.Recv(*dst + off, nk, ncclChar, k, hc->comm, st));
+      off += nk;
+    }
+    SF_NCCL(a.GroupEnd());
+  } else if (nbytes) {
+    SF_NCCL(a.GroupStart());
+    SF_NCCL(a.Send(src, nbytes, ncclChar, 0, hc->comm, st));
+    SF_NCCL(a.GroupEnd());
+  }
+  return total;
 }
 
 extern "C" {

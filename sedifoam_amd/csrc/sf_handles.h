@@ -24,8 +24,12 @@ struct SfLammps {
   // sees the RCCL headers
   void* halo = nullptr;
   void (*halo_delete)(void*) = nullptr;
+  // the `dump` commands and their writer thread (sf_dump.hip); opaque here like halo
+  void* dumps = nullptr;
+  void (*dumps_delete)(void*) = nullptr;
   ~SfLammps()
   {
+    if (dumps && dumps_delete) dumps_delete(dumps);   // (drains the writer: the frames are in their files)
     if (halo && halo_delete) halo_delete(halo);
   }
 };

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/sedifoam_amd.h"
+#include "sf_dump.h"
 #include "sf_handles.h"
 #include "sf_roctx.h"
 
@@ -122,7 +123,7 @@ int brick_owner(const SfLammps& L, const double* x)
 
 // "run n pre no post no" on whatever the engine is: one domain, or the bricks of a -parallel run (library.cpp:372-386
 // is collective there: Verlet::run with its forward communication and the reneighbouring vote)
-void run_steps(SfLammps& L, int n)
+void advance(SfLammps& L, int n)
 {
   if (!L.decomposed && sf_slab_active(&L) != 1) {   // (a host may also have set the domains up itself: sf_slab_init)
     L.eng.run(n);
@@ -135,6 +136,31 @@ void run_steps(SfLammps& L, int n)
   }
   if (sf_slab_step(&L, n) != 0) sf::fail("%s", sf::last_error().c_str());
 }
+
+}  // namespace
+
+// ... with the frames of the active dumps: the run is cut at every step a dump writes (a queued batch ends there with
+// the end-of-step state: sub-step s with last = 1, then the dump kernels, then the next piece begins with its initial
+// integrate -- what consecutive `run N pre no post no` calls do), and the frame of the current step is written first
+// if it is due ([3P] Output::setup: step 0 at the setup of the first run)
+void sf::run_steps(SfLammps& L, int n)
+{
+  if (!sf::dump_active(L)) {
+    advance(L, n);
+    return;
+  }
+  advance(L, 0);   // (setup: the frame of the first step holds the forces of the setup evaluation)
+  sf::dump_write_due(L);
+  const long long end = L.eng.nsteps() + (n > 0 ? n : 0);
+  while (L.eng.nsteps() < end) {
+    long long next = sf::dump_next_step(L, L.eng.nsteps());
+    if (next < 0 || next > end) next = end;
+    advance(L, (int)(next - L.eng.nsteps()));
+    sf::dump_write_due(L);
+  }
+}
+
+namespace {
 
 // atom->natoms after atoms came or went: the sum of nlocal over the ranks (library.cpp:470-473)
 void recount_atoms(SfLammps& L)
@@ -407,6 +433,13 @@ void command(SfLammps& L, const std::string& line)
   } else if (c == "run") {
     if (w.size() < 2) sf::fail("Illegal run command");
     run_steps(L, inum(w[1]));
+    sf::dump_drain(L);   // (a script's run returns with its frames in their files)
+  } else if (c == "dump") {
+    sf::dump_command(L, w);
+  } else if (c == "dump_modify") {
+    sf::dump_modify_command(L, w);
+  } else if (c == "undump") {
+    sf::undump_command(L, w);
   } else if (c == "processors") {
     // [3P] processors px py pz (`*` = chosen by LAMMPS); must come before the box is created, like in LAMMPS
     if (w.size() < 4) sf::fail("Illegal processors command");
@@ -419,8 +452,7 @@ void command(SfLammps& L, const std::string& line)
         L.procgrid[0] * L.procgrid[1] * L.procgrid[2] != L.world_size && L.world_size > 1)
       sf::fail("Specified processors != physical processors");   // [3P] Comm::set_proc_grid
   } else if (c == "pair_coeff" || c == "atom_modify" || c == "thermo" ||
-             c == "thermo_style" || c == "thermo_modify" || c == "dump" || c == "dump_modify" ||
-             c == "restart" || c == "echo" || c == "log" || c == "dimension") {
+             c == "thermo_style" || c == "thermo_modify" || c == "restart" || c == "echo" || c == "log" || c == "dimension") {
     // accepted, nothing to do on this path
   } else
     sf::fail("Unknown command: %s", c.c_str());
@@ -529,6 +561,7 @@ int sf_lammps_sync(void* ptr)
 {
   SF_API_BEGIN
   SF_HIP(hipStreamSynchronize(H(ptr)->eng.stream()));
+  sf::dump_drain(*H(ptr));   // (and the dump frames queued so far are in their files)
   SF_API_END(0)
 }
 

@@ -93,6 +93,10 @@ class Lammps:
     def step(self, n):
         check(self.L.sf_lammps_step(self.ptr, int(n)))
 
+    def sync(self):
+        """wait for the engine's stream and for the dump frames queued so far to be in their files"""
+        check(self.L.sf_lammps_sync(self.ptr))
+
     def set_timestep(self, dt):
         check(self.L.sf_lammps_set_timestep(self.ptr, float(dt)))
 
