@@ -180,6 +180,12 @@ inline void lammps_step(void* ptr, int n)
 }
 inline void lammps_set_timestep(void* ptr, double dt_i) { sf_lammps_set_timestep(sedifoam_shim::h(ptr), dt_i); }
 inline double lammps_get_timestep(void* ptr) { return sf_lammps_get_timestep(sedifoam_shim::h(ptr)); }
+/* the modern LAMMPS name: a thermo keyword's value in the last thermo line written (0.0 when there is none) */
+inline double lammps_get_thermo(void* ptr, const char* keyword)
+{
+  double v = 0.0;
+  return sf_lammps_get_thermo(sedifoam_shim::h(ptr), keyword, &v) == 0 ? v : 0.0;
+}
 inline void lammps_create_particle(void* ptr, int npAdd, double* position, double* tag, double diameter,
                                    double rho, int type, double* vel)
 {

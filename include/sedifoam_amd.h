@@ -68,7 +68,9 @@ int sf_lammps_file(void *ptr, const char *path);
  * communicate, processors, read_data (or sf_dem_create_atoms), neighbor, neigh_modify, pair_style {gran/hertzFix/history,
  * gran/hooke/history, lubricate/poly, hybrid/overlay}, pair_coeff, timestep, velocity all set,
  * fix {nve/sphere, gravity, fdrag, freeze, cohesive, wall/gran and wall/granFix ({x,y,z}plane | zcylinder, wiggle | shear)},
- * group {type, subtract, union, intersect}, run; thermo*, dump and restart are accepted without effect.
+ * group {type, subtract, union, intersect}, run, dump custom, thermo / thermo_style / thermo_modify, units, log,
+ * echo; restart is accepted without effect.  argv: -screen none|stdout|FILE and -log none|FILE (default none, see
+ * INTEGRATION.md).
  * Returns NULL like LAMMPS, or an error string. */
 const char *sf_lammps_command(void *ptr, const char *line);
 /* library.h:34 (debug barrier) -- a stream synchronise here */
@@ -96,6 +98,12 @@ int sf_lammps_step(void *ptr, int n);
 /* library.h:59-60 */
 int sf_lammps_set_timestep(void *ptr, double dt_i);
 double sf_lammps_get_timestep(void *ptr);
+/* thermo output: the value of a `thermo_style custom` keyword (step, temp, press, ke, pxx, fmax, ...) in the last thermo
+ * line written -- what LAMMPS' lammps_get_thermo returns; -1 before the first line or for an unknown keyword.  Lines are
+ * computed only while a destination is open (`log FILE`, -screen / -log of sf_lammps_open, SF_SCREEN / SF_LOG). */
+int sf_lammps_get_thermo(void *ptr, const char *keyword, double *out);
+/* kernel launches made for thermo lines so far (the virial pass and the reductions): 0 while no destination is open */
+int sf_lammps_thermo_launches(void *ptr, long long *launches);
 /* library.h:61-63 (particle injection / removal; tag[] is double in the reference) */
 int sf_lammps_create_particle(void *ptr, int npAdd, const double *position, const double *tag,
                               double diameter, double rho, int type, const double *vel);
@@ -541,6 +549,8 @@ static inline void lammps_put_local_info(void *p, int n, double *fd, double *du,
 static inline void lammps_step(void *p, int n) { sf_lammps_step(p, n); }
 static inline void lammps_set_timestep(void *p, double dt) { sf_lammps_set_timestep(p, dt); }
 static inline double lammps_get_timestep(void *p) { return sf_lammps_get_timestep(p); }
+static inline double lammps_get_thermo(void *p, const char *k)
+{ double v = 0.0; return sf_lammps_get_thermo(p, k, &v) == 0 ? v : 0.0; }
 static inline void lammps_create_particle(void *p, int n, double *x, double *t, double d,
                                           double r, int ty, double *v)
 { sf_lammps_create_particle(p, n, x, t, d, r, ty, v); }

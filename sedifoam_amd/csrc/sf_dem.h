@@ -579,6 +579,13 @@ class DemEngine {
   // neighbour rebuilds inside runs while profiling was on: how many, and their summed duration on the host clock, from
   // the trigger read to the end of the last kernel of the rebuild (synchronised: only while profiling)
   void get_rebuild_profile(long long* rebuilds, double* ms);
+  // thermo output (sf_thermo.hip): while armed, the setup evaluation (mode 2) and every mode-1 launch -- the last
+  // sub-step of a piece -- are preceded by k_thermo_virial on the same inputs, which tallies that force evaluation's pair
+  // virial into per-block partials.  A mode-1 launch behind a trigger runs again after the rebuild, and so does the pass.
+  void set_thermo_virial(bool on) { thermo_virial_on_ = on; }
+  const double* thermo_virial_partials() const { return thermo_vbuf_; }
+  int thermo_virial_blocks() const { return thermo_vblocks_; }   // partial rows of the last pass (0: no owned atoms)
+  long long thermo_virial_launches() const { return thermo_vlaunches_; }
 
  private:
   void ensure_capacity(size_t need);
@@ -838,6 +845,11 @@ private:
   long long prof_launches_ = 0;
   double prof_ms_ = 0.0;
   void harvest_profile(int last_step);
+  bool thermo_virial_on_ = false;
+  double* thermo_vbuf_ = nullptr;      // [blocks][6] partials of k_thermo_virial
+  int thermo_vblocks_ = 0;
+  long long thermo_vlaunches_ = 0;
+  void launch_thermo_virial(const DemPtrs& P, const StepParams& S);
 };
 
 // sf_sort.hip

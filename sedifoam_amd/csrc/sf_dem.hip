@@ -16,6 +16,7 @@
 #include "sf_dem_io.h"
 #include "sf_dem_lds_kernel.h"
 #include "sf_roctx.h"
+#include "sf_thermo.h"
 
 namespace sf {
 
@@ -161,6 +162,7 @@ DemEngine::~DemEngine()
     }
   }
 #endif
+  if (thermo_vbuf_) (void)hipFree(thermo_vbuf_);
   if (d_xcd_time_) (void)hipFree(d_xcd_time_);
   if (d_pq_head_) (void)hipFree(d_pq_head_);
   if (h_xcd_time_) (void)hipHostFree(h_xcd_time_);
@@ -988,9 +990,21 @@ int DemEngine::lanes_per_atom(int nwork) const
   return 0.55 * std::ceil(2.0 * r) < std::ceil(r) ? 2 : 1;
 }
 
+void DemEngine::launch_thermo_virial(const DemPtrs& P, const StepParams& S)
+{
+  if (!thermo_vbuf_) SF_HIP(hipMalloc(&thermo_vbuf_, sizeof(double) * 6 * ::sf::thermo_virial_blocks(INT_MAX)));
+  thermo_vblocks_ = ::sf::thermo_virial_blocks(nlocal_);
+  thermo_virial_launch(P, S, lub_.enabled != 0, thermo_vbuf_, thermo_vblocks_, stream_);
+  thermo_vlaunches_++;
+}
+
 void DemEngine::launch_substep(int in_buf, int mode, int kstep, int part)
 {
   if (!nlocal_) {
+    if (thermo_virial_on_ && mode != 0) {   // (thermo: a virial pass over no atoms, zero rows)
+      thermo_vblocks_ = 0;
+      thermo_vlaunches_++;
+    }
     // (ghost slots: the other ranks wait for this one's flag whether it owns atoms or not)
     if (gs_ready_ && brick_ && part == 0 && !lds_active_ && mode != 2) {
       k_gs_idle<<<1, 64, 0, stream_>>>(d_gs_sync_, d_flags_, (int)gs_seq_, kstep, mode == 0 ? 1 : 0);
@@ -1002,6 +1016,10 @@ void DemEngine::launch_substep(int in_buf, int mode, int kstep, int part)
   if (part == 2 && !nb_) return;   // (no event pair opened: the interior part then times itself)
   DemPtrs P = ptrs(in_buf);
   StepParams S = step_params(mode, kstep);
+  // thermo output: the pair virial of this force evaluation, from the inputs it reads (an overlapped sub-step: before its
+  // boundary part, which the driver queues behind the ghosts of the previous exchange; before the interior part only
+  // when there is no boundary part)
+  if (thermo_virial_on_ && mode != 0 && (part != 1 || !nb_)) launch_thermo_virial(P, S);
   // ghost slots: every stepping launch of a decomposed engine reads the ghosts of other GPUs from the area of its number's
   // parity and (mode 0) writes its border records into the neighbours' area of the next parity; the setup evaluation
   // (mode 2) runs on the ghosts the border exchange has just put into the record arrays

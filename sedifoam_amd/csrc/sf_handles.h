@@ -27,8 +27,12 @@ struct SfLammps {
   // the `dump` commands and their writer thread (sf_dump.hip); opaque here like halo
   void* dumps = nullptr;
   void (*dumps_delete)(void*) = nullptr;
+  // thermo settings, destinations and the last line (sf_thermo.hip); opaque here like halo
+  void* thermo = nullptr;
+  void (*thermo_delete)(void*) = nullptr;
   ~SfLammps()
   {
+    if (thermo && thermo_delete) thermo_delete(thermo);   // (closes the log and screen files)
     if (dumps && dumps_delete) dumps_delete(dumps);   // (drains the writer: the frames are in their files)
     if (halo && halo_delete) halo_delete(halo);
   }

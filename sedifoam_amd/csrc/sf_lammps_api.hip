@@ -17,6 +17,7 @@
 #include "sf_dump.h"
 #include "sf_handles.h"
 #include "sf_roctx.h"
+#include "sf_thermo.h"
 
 using sf::DemEngine;
 using sf::SfLammps;
@@ -139,25 +140,36 @@ void advance(SfLammps& L, int n)
 
 }  // namespace
 
-// ... with the frames of the active dumps: the run is cut at every step a dump writes (a queued batch ends there with
-// the end-of-step state: sub-step s with last = 1, then the dump kernels, then the next piece begins with its initial
-// integrate -- what consecutive `run N pre no post no` calls do), and the frame of the current step is written first
-// if it is due ([3P] Output::setup: step 0 at the setup of the first run)
+// ... with the frames of the active dumps and the thermo lines: the run is cut at every step a dump or thermo writes (a
+// queued batch ends there with the end-of-step state: sub-step s with last = 1, then the dump kernels / the thermo
+// reduction, then the next piece begins with its initial integrate -- what consecutive `run N pre no post no` calls do),
+// and the frame of the current step is written first if it is due ([3P] Output::setup: step 0 at the setup of the first
+// run).  Without a dump and without a thermo destination the run is not cut.
 void sf::run_steps(SfLammps& L, int n)
 {
-  if (!sf::dump_active(L)) {
+  const bool thermo = sf::thermo_active(L);
+  if (!sf::dump_active(L) && !thermo) {
+    L.eng.set_thermo_virial(false);
     advance(L, n);
     return;
   }
+  if (thermo) sf::thermo_run_begin(L);   // (the first run: the virial of the setup evaluation)
   advance(L, 0);   // (setup: the frame of the first step holds the forces of the setup evaluation)
   sf::dump_write_due(L);
+  if (thermo) sf::thermo_setup(L, n);
   const long long end = L.eng.nsteps() + (n > 0 ? n : 0);
   while (L.eng.nsteps() < end) {
     long long next = sf::dump_next_step(L, L.eng.nsteps());
     if (next < 0 || next > end) next = end;
+    if (thermo) {
+      next = std::min(next, sf::thermo_next_step(L, L.eng.nsteps()));
+      sf::thermo_arm(L, next);   // (the pair virial of step `next`, when it has a line that shows pressure)
+    }
     advance(L, (int)(next - L.eng.nsteps()));
     sf::dump_write_due(L);
+    if (thermo) sf::thermo_write_due(L);
   }
+  if (thermo) sf::thermo_run_end(L);
 }
 
 namespace {
@@ -382,11 +394,14 @@ void cmd_group(SfLammps& L, const std::vector<std::string>& w)
 
 void command(SfLammps& L, const std::string& line)
 {
+  sf::thermo_echo(L, line);
   std::vector<std::string> w = split(line);
   if (w.empty()) return;
   const std::string& c = w[0];
+  if (sf::thermo_command(L, w)) return;   // thermo, thermo_style, thermo_modify, log, echo (sf_thermo.hip)
   if (c == "units") {
     if (w.size() != 2 || (w[1] != "lj" && w[1] != "si")) sf::fail("units %s not supported (lj | si: nktv2p = 1)", w.size() > 1 ? w[1].c_str() : "");
+    sf::thermo_units(L, w[1] == "lj");
   } else if (c == "atom_style") {
     if (w.size() < 2 || w[1] != "sphere") sf::fail("atom_style must be sphere");
   } else if (c == "newton") {
@@ -418,7 +433,9 @@ void command(SfLammps& L, const std::string& line)
     cmd_pair_style(L, w, 1);
   } else if (c == "timestep") {
     if (w.size() != 2) sf::fail("Illegal timestep command");
-    L.eng.set_timestep(num(w[1]));
+    const double dt = num(w[1]);
+    sf::thermo_update_time(L);
+    L.eng.set_timestep(dt);
   } else if (c == "velocity") {
     if (w.size() >= 6 && w[2] == "set") {
       for (int k = 3; k < 6; k++)
@@ -451,8 +468,7 @@ void command(SfLammps& L, const std::string& line)
     if (L.procgrid[0] && L.procgrid[1] && L.procgrid[2] &&
         L.procgrid[0] * L.procgrid[1] * L.procgrid[2] != L.world_size && L.world_size > 1)
       sf::fail("Specified processors != physical processors");   // [3P] Comm::set_proc_grid
-  } else if (c == "pair_coeff" || c == "atom_modify" || c == "thermo" ||
-             c == "thermo_style" || c == "thermo_modify" || c == "restart" || c == "echo" || c == "log" || c == "dimension") {
+  } else if (c == "pair_coeff" || c == "atom_modify" || c == "restart" || c == "dimension") {
     // accepted, nothing to do on this path
   } else
     sf::fail("Unknown command: %s", c.c_str());
@@ -482,16 +498,22 @@ int sf_device_check(void)
   return 0;
 }
 
-int sf_lammps_open(int, char**, intptr_t comm, void** ptr)
+int sf_lammps_open(int argc, char** argv, intptr_t comm, void** ptr)
 {
   SF_API_BEGIN
   SfLammps* L = new SfLammps();
   L->comm = comm;
+  try {
+    sf::thermo_open_args(*L, argc, argv);   // -screen / -log (SF_SCREEN / SF_LOG)
+  } catch (...) {
+    delete L;
+    throw;
+  }
   *ptr = L;
   SF_API_END(0)
 }
 
-int sf_lammps_open_world(int, char**, intptr_t comm, int rank, int world, const char* id128, void** ptr)
+int sf_lammps_open_world(int argc, char** argv, intptr_t comm, int rank, int world, const char* id128, void** ptr)
 {
   SF_API_BEGIN
   if (world < 1 || rank < 0 || rank >= world) sf::fail("sf_lammps_open_world: rank %d of %d", rank, world);
@@ -515,6 +537,12 @@ int sf_lammps_open_world(int, char**, intptr_t comm, int rank, int world, const 
   L->world_rank = rank;
   L->world_size = world;
   if (id128) memcpy(L->comm_id, id128, 128);
+  try {
+    sf::thermo_open_args(*L, argc, argv);   // (rank 0 opens the files)
+  } catch (...) {
+    delete L;
+    throw;
+  }
   *ptr = L;
   SF_API_END(0)
 }
@@ -646,6 +674,24 @@ int sf_lammps_set_timestep(void* ptr, double dt_i)
 {
   SF_API_BEGIN
   H(ptr)->eng.set_timestep(dt_i);
+  SF_API_END(0)
+}
+
+int sf_lammps_get_thermo(void* ptr, const char* keyword, double* out)
+{
+  SF_API_BEGIN
+  if (!keyword || !out) sf::fail("sf_lammps_get_thermo: null argument");
+  const int r = sf::thermo_get(*H(ptr), keyword, out);
+  if (r == -2) sf::fail("sf_lammps_get_thermo: unknown thermo keyword %s", keyword);
+  if (r == -1) sf::fail("sf_lammps_get_thermo: no thermo line has been written yet");
+  SF_API_END(0)
+}
+
+int sf_lammps_thermo_launches(void* ptr, long long* launches)
+{
+  SF_API_BEGIN
+  if (!launches) sf::fail("sf_lammps_thermo_launches: null argument");
+  *launches = sf::thermo_launches(*H(ptr));
   SF_API_END(0)
 }
 

@@ -26,10 +26,13 @@ def _p(a):
 class Lammps:
     """`lammps_open` ... `lammps_close` (library.h:29-63)."""
 
-    def __init__(self, comm=0):
+    def __init__(self, comm=0, args=None):
+        """args: LAMMPS command-line arguments after the program name, e.g. ["-log", "log.lammps", "-screen", "none"]"""
         self.L = _lib.lib()
         h = C.c_void_p()
-        check(self.L.sf_lammps_open(0, None, comm, C.byref(h)))
+        argv = [b"sedifoam_amd"] + [str(a).encode() for a in (args or [])]
+        arr = (C.c_char_p * (len(argv) + 1))(*argv, None)
+        check(self.L.sf_lammps_open(len(argv), C.cast(arr, C.c_void_p), comm, C.byref(h)))
         self.ptr = h
 
     def close(self):
@@ -102,6 +105,18 @@ class Lammps:
 
     def get_timestep(self):
         return self.L.sf_lammps_get_timestep(self.ptr)
+
+    def get_thermo(self, keyword):
+        """a thermo keyword's value in the last thermo line written (lammps_get_thermo)"""
+        v = C.c_double()
+        check(self.L.sf_lammps_get_thermo(self.ptr, keyword.encode(), C.byref(v)))
+        return v.value
+
+    def thermo_launches(self):
+        """kernel launches made for thermo lines so far"""
+        n = C.c_longlong()
+        check(self.L.sf_lammps_thermo_launches(self.ptr, C.byref(n)))
+        return n.value
 
     def create_particle(self, position, tag, diameter, rho, type_, vel):
         position = _f64(position).reshape(-1, 3)
