@@ -48,6 +48,19 @@ __host__ __device__ __forceinline__ int neigh_index(int word, int roots)
 {
   return roots ? (word & kIdxMask) : (word & kNeighMask);
 }
+// a root's record moved to the periodic image that the code bits of its list word name (prd: the box lengths) -- the same
+// x_root + shift the reference's forward_comm would have stored.  Root mode, owner-side words only: the code bits of a
+// partner-side word hold the owner's slot (a partner-side neighbour is never an image).
+__device__ __forceinline__ void shift_to_image(double4& x, const int word, const double (&prd)[3])
+{
+  const int code = (word >> kIdxBits) & 31;
+  if (code != kNoShift) {
+    const int cz = code / 9, cy = (code - 9 * cz) / 3, cx = code - 9 * cz - 3 * cy;
+    x.x += (double)(cx - 1) * prd[0];
+    x.y += (double)(cy - 1) * prd[1];
+    x.z += (double)(cz - 1) * prd[2];
+  }
+}
 constexpr int kMaxWalls = 6;
 
 enum Flag {
@@ -147,8 +160,6 @@ struct DemPtrs {
                                 // neighbour's uncached area is made of
   const int* tx_hdr_off;
   int* xcd_time;                // StepParams::xcd_time: [64 x + 0] first start, [64 x + 32] last end of XCD x (100 MHz clock)
-  int* pq_head;                 // persistent tiles (k_substep_persist): [2][8][32] -- per launch parity and XCD one head word
-                                // on a line of its own: the next tile of that XCD's range nobody has taken yet
   // ghost slots (StepParams::gs_on, sf_halo_rccl.hip, sf_dem_gs.h): the neighbours' sub-step kernels write the records of
   // this rank's ghosts straight into the ghost range of xr / vm / om.  On the sending side tx_blkptr is then [3][kMaxDirs]:
   // where block q's first x | v | omega record goes in the NEIGHBOUR's arrays (the buffer its launch of the next number
@@ -197,9 +208,7 @@ struct StepParams {
                    // size -- XCD x works on the xcd_count[x] blocks from xcd_first[x], the grid is 8 x the largest count
                    // and a workgroup beyond its XCD's count exits at once
   int xcd_first[8], xcd_count[8];
-  int sweep_rev;   // walk each XCD's range backwards (every other sub-step)
   int xcd_time;    // this launch records when each XCD starts and ends (DemPtrs::xcd_time): the engine balances the shares
-  int pq_par;      // persistent tiles: which of the two sets of head words this launch pulls from (it zeroes the other one)
   WallParams wall[kMaxWalls];
   int have_gravity;
   double gacc[3];
@@ -740,11 +749,6 @@ private:
   int opt_ghost_free_ = -1;
   bool ghost_free_ = false;
   int nimages_ = -1;                         // ghost_free_: images counted for nghost() (-1: not counted since the last rebuild)
-  int opt_persist_ = -1;                     // SF_PERSIST: persistent tiles (k_substep_persist) off (0), on wherever the kernel
-                                             // exists (1), default (-1): where it measured faster (launch_substep)
-  int opt_persist_waves_ = 0;                // SF_PERSIST_WAVES: waves per XCD of the persistent launch (0: the resident ones)
-  int* d_pq_head_ = nullptr;                 // [2][8][32] head words of the persistent launch (DemPtrs::pq_head)
-  int pq_par_ = 0;
   bool in_run_ = false;                      // rebuild() called from the stepping loop of run()
   RebuildPredictor predict_;                 // single-domain run(): how far to queue (SF_QUEUE_PREDICT=0: everything)
   int nt_policy_ = 2, nt_policy_env_ = -1;   // non-temporal policy of the row streams (sf_dem_kernels.h, NTP)

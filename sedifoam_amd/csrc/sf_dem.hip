@@ -130,10 +130,6 @@ DemEngine::DemEngine()
   if (const char* e = getenv("SF_NT_POLICY")) nt_policy_env_ = atoi(e);
   if (const char* e = getenv("SF_LPA")) opt_lpa_ = atoi(e);
   if (const char* e = getenv("SF_GHOST_FREE")) opt_ghost_free_ = atoi(e);
-  if (const char* e = getenv("SF_PERSIST")) opt_persist_ = atoi(e);
-  if (const char* e = getenv("SF_PERSIST_WAVES")) opt_persist_waves_ = atoi(e);
-  SF_HIP(hipMalloc(&d_pq_head_, sizeof(int) * 2 * 8 * 32));
-  SF_HIP(hipMemsetAsync(d_pq_head_, 0, sizeof(int) * 2 * 8 * 32, stream_));
   if (const char* e = getenv("SF_QUEUE_PREDICT")) predict_.on = atoi(e) != 0;
   memset(&gran_, 0, sizeof(gran_));
   memset(&cohe_, 0, sizeof(cohe_));
@@ -164,7 +160,6 @@ DemEngine::~DemEngine()
 #endif
   if (thermo_vbuf_) (void)hipFree(thermo_vbuf_);
   if (d_xcd_time_) (void)hipFree(d_xcd_time_);
-  if (d_pq_head_) (void)hipFree(d_pq_head_);
   if (h_xcd_time_) (void)hipHostFree(h_xcd_time_);
   bslot_.release();   // (not in per_atom_: allocated by the first brick rebuild, re-allocated when the capacity moves)
   if (cell_start_) (void)hipFree(cell_start_);
@@ -818,7 +813,6 @@ DemPtrs DemEngine::ptrs(int in_buf) const
   P.gs_my_sync = nullptr;
   P.gs_count = nullptr;
   P.xcd_time = d_xcd_time_;
-  P.pq_head = d_pq_head_;
   P.tile_last = tile_tab_ ? tile_tab_ + tile_alloc_ : nullptr;
   P.stage_start = tile_tab_ ? tile_tab_ + 3 * tile_alloc_ : nullptr;
   P.stage_idx = stage_idx_;
@@ -849,8 +843,6 @@ StepParams DemEngine::step_params(int mode, int kstep) const
   S.lub = lub_;
   S.nwalls = nwalls_;
   S.xcd_remap = opt_xcd_remap_;
-  static const int sweep_env = getenv("SF_SWEEP_REVERSE") ? atoi(getenv("SF_SWEEP_REVERSE")) : 0;   // (measured neutral at 1 M grains: off)
-  S.sweep_rev = (sweep_env && mode != 2) ? (int)((run_base_step_ + kstep) & 1) : 0;
   S.stage_cap = stage_cap_;
   // wall positions / velocities of the LAMMPS step this launch evaluates: post_force of step n sees ntimestep = n,
   // the setup evaluation sees the value the run starts from (fix_wall_granFix.cpp:255-264)
@@ -926,25 +918,6 @@ static void launch_substep_style(bool cohe, bool lub, int lpa, bool tp, int ntp,
   else if (ntp == 3) launch_substep_tp<STYLE, 1, 3>(cohe, lub, tp, grid, block, s, P, S);
   else launch_substep_tp<STYLE, 1, 2>(cohe, lub, tp, grid, block, s, P, S);
 }
-
-#ifdef SF_EXP_PERSIST
-// persistent tiles (k_substep_persist): the plain Hertz contact kernel, one lane per atom
-static void launch_substep_persist(bool tp, int ntp, dim3 grid, hipStream_t s, const DemPtrs& P, const StepParams& S)
-{
-  if (tp) {
-    if (ntp == 0) k_substep_persist<2, false, false, true, 0><<<grid, 64, 0, s>>>(P, S);
-    else if (ntp == 1) k_substep_persist<2, false, false, true, 1><<<grid, 64, 0, s>>>(P, S);
-    else if (ntp == 3) k_substep_persist<2, false, false, true, 3><<<grid, 64, 0, s>>>(P, S);
-    else k_substep_persist<2, false, false, true, 2><<<grid, 64, 0, s>>>(P, S);
-  } else {
-    if (ntp == 0) k_substep_persist<2, false, false, false, 0><<<grid, 64, 0, s>>>(P, S);
-    else if (ntp == 1) k_substep_persist<2, false, false, false, 1><<<grid, 64, 0, s>>>(P, S);
-    else if (ntp == 3) k_substep_persist<2, false, false, false, 3><<<grid, 64, 0, s>>>(P, S);
-    else k_substep_persist<2, false, false, false, 2><<<grid, 64, 0, s>>>(P, S);
-  }
-}
-
-#endif
 
 template <int STYLE, bool COHE, bool LUB>
 static void launch_lds_one(dim3 grid, size_t lds, hipStream_t s, const DemPtrs& P, const StepParams& S)
@@ -1156,32 +1129,6 @@ void DemEngine::launch_substep(int in_buf, int mode, int kstep, int part)
       grid = dim3((unsigned)(8 * most));
     }
     stamp_last_grid_ = grid.x;
-#ifdef SF_EXP_PERSIST
-    // Persistent tiles: the resident waves walk the tiles of their XCD's range and request the next tile's records under
-    // the current tile's epilogue (k_substep_persist).  The plain Hertz kernel with one lane per atom and one-wave tiles,
-    // when the launch is at least three rounds of resident waves.
-    static const int resident_per_xcd = [] {
-      int dev = 0, cus = 256;
-      if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-      return std::max(1, cus * 4 * 3 / 8);
-    }();
-    const int pw = opt_persist_waves_ > 0 ? opt_persist_waves_ : resident_per_xcd;
-    const int tiles = (int)((lanes + 63) / 64);
-    const bool persist = opt_persist_ != 0 && !gs && part == 0 && lpa == 1 && block == 64 && gran_.style == 2 && !cohe &&
-                         !lub && S.xcd_remap != 0 && mode != 2 && (opt_persist_ == 1 || tiles >= 3 * 8 * pw);
-    if (persist) {
-      if (S.xcd_remap == 1) {   // equal shares: the ranges xcd_contiguous_block() gives
-        const int q = tiles >> 3, r = tiles & 7;
-        for (int x = 0; x < 8; x++) {
-          S.xcd_count[x] = x < r ? q + 1 : q;
-          S.xcd_first[x] = x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-        }
-      }
-      S.pq_par = pq_par_;
-      pq_par_ ^= 1;
-      launch_substep_persist(touch_prefetch_, nt_policy_, dim3((unsigned)(8 * pw)), stream_, P, S);
-    } else
-#endif
     switch (gran_.style) {
       case 2: launch_substep_style<2>(cohe, lub, lpa, touch_prefetch_, nt_policy_, grid, block, stream_, P, S); break;
       case 3:

@@ -19,10 +19,6 @@ namespace sf {
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void gs_store(double4* p, double a, double b, double c, double d)
 {
-#ifdef SF_GS_EXP_PLAIN_STORE   // (pricing arm of tests/ab_gs_arms.sh: not a correct hand-off)
-  *p = double4{a, b, c, d};
-  return;
-#endif
   // two 16-byte write-through system-scope stores per record (`global_store_dwordx4 ... sc0 sc1`; HIP has no builtin for a
   // 16-byte store with scope bits: four 8-byte atomic stores cost 1 us more per sub-step on the 126 k brick).  The
   // compiler does not count them in vmcnt: the hand-off drains them with its own `s_waitcnt vmcnt(0)` (gs_done / the end
@@ -120,12 +116,7 @@ __device__ __forceinline__ void gs_publish(const GsSync* Y, const int vote, cons
 __device__ __forceinline__ void gs_done(const DemPtrs& P, const StepParams& S, const bool wrote, const bool triggered,
                                         const bool poller, const int expected_lane)
 {
-#ifdef SF_GS_EXP_NODONE
-  return;
-#endif
-#ifndef SF_GS_EXP_NOWAIT
   if (__ballot(wrote)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
   const int lane = threadIdx.x & 63;
   const unsigned long long trig = __ballot(triggered) ? (1ull << 32) : 0ull;
   unsigned long long* cnt = reinterpret_cast<unsigned long long*>(P.gs_count);

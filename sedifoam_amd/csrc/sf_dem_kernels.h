@@ -11,41 +11,14 @@
 
 #include "sf_dem.h"
 
-// Compile-time variants of the sub-step kernel; the defaults are the measured best, the
-// others are built next to the shipped library by tests/build_variant.sh for A/B runs.
-#ifndef SF_UNROLL2
-#define SF_UNROLL2 1          // neighbour loop unrolled by two: the prefetch ping-pongs between two register sets
-#endif
-#ifndef SF_NT
-#define SF_NT 1               // read-once rows as non-temporal loads
-#endif
-#ifndef SF_NT_ST
-#define SF_NT_ST SF_NT        // write-once rows as non-temporal stores
-#endif
-#ifndef SF_NT_OUT
-#define SF_NT_OUT 0           // output records non-temporal too (slower: the next sub-step gathers them)
-#endif
-#ifndef SF_ST_SHUFFLE
-#define SF_ST_SHUFFLE 1       // output records exchanged between lanes so that every store covers whole cache lines
-#endif
-// (whether v, omega of a neighbour are prefetched always or only when the pair touched one sub-step ago is the template
-// parameter TP of k_substep, chosen per list from the fraction of listed neighbours that touch)
-#ifndef SF_HIST_PREFETCH
-#define SF_HIST_PREFETCH 1    // the history of slot s+1 is requested with the records of slot s+1, one contact evaluation ahead
-#endif
-#ifndef SF_PERS_PREFETCH
-#define SF_PERS_PREFETCH 1    // k_substep_persist: the next tile's records are requested under the current tile's epilogue
-#endif
-#ifndef SF_PERS_DYNAMIC
-#define SF_PERS_DYNAMIC 1     // k_substep_persist: tiles beyond a wave's first two come from the XCD's head word (0: by position)
-#endif
-#ifndef SF_COOP_GATHER
-#define SF_COOP_GATHER 1      // a neighbour's 32-byte record is read by the two lanes l, l + 32 together (see coop_merge)
-#endif
 // Instrumentation of variant builds (tests/build_variant.sh): SF_EXP_STAMP / SF_EXP_PHASE, the workgroup timeline of one
 // launch -- sf_dem_variants.h.  The pricing arms of rounds 1-4 (history traffic off, agent-coherent access forms, LDS-DMA
 // row streams, the no-wait persistent kernel, neighbour records by lane shuffle, the two-lane launch tail) were measured,
-// written up (docs/history_r01_r03.md, profiles/r04_README.md, profiles/r05_README.md) and removed from this file.
+// written up (docs/history_r01_r03.md, profiles/r04_README.md, profiles/r05_README.md) and removed from this file.  So were
+// those of rounds 5 and 6 (profiles/r05_README.md, profiles/r06_README.md): the persistent-tile kernel,
+// the ghost-slot hand-off with one part compiled out, the reversed sweep, and the compile-time switches of the neighbour
+// loop and its stores (unroll by two, non-temporal rows, shuffled stores, history prefetch, half-wave gather, lean
+// variants, waves per SIMD), which keep their measured defaults.
 #include "sf_dem_variants.h"
 #include "sf_dem_gs.h"
 
@@ -55,10 +28,7 @@ __device__ __forceinline__ Vec3 v3(const double4& a) { return {a.x, a.y, a.z}; }
 
 // one lane per atom with exactly one of the cohesive / lubrication arms: the lean loop at three waves per SIMD (see
 // substep_particle); the kernels of small systems (several lanes per atom) and the one with both arms stay as they were
-#ifndef SF_LEAN_VARIANTS
-#define SF_LEAN_VARIANTS 1
-#endif
-constexpr bool sf_lean_variant(bool cohe, bool lub, int lpa) { return SF_LEAN_VARIANTS && lpa == 1 && cohe != lub; }
+constexpr bool sf_lean_variant(bool cohe, bool lub, int lpa) { return lpa == 1 && cohe != lub; }
 
 // Streamed (read-once / write-once per sub-step) rows can be marked non-temporal so that they do not evict the
 // neighbour records the gathers want to find again in the 32 KB vector L1 and the 4 MB L2 of the XCD.  Whether that
@@ -75,25 +45,14 @@ constexpr bool sf_lean_variant(bool cohe, bool lub, int lpa) { return SF_LEAN_VA
 template <bool NT, class T>
 __device__ __forceinline__ T ld_stream(const T* p)
 {
-  if (NT && SF_NT) return __builtin_nontemporal_load(p);
+  if (NT) return __builtin_nontemporal_load(p);
   return *p;
 }
 template <bool NT, class T>
 __device__ __forceinline__ void st_stream(T* p, T v)
 {
-  if (NT && SF_NT_ST) __builtin_nontemporal_store(v, p);
+  if (NT) __builtin_nontemporal_store(v, p);
   else *p = v;
-}
-template <bool NT>
-__device__ __forceinline__ void st_stream4(double4* p, double4 v)
-{
-  if (NT && SF_NT) {
-    typedef double d4v __attribute__((ext_vector_type(4)));
-    d4v t = {v.x, v.y, v.z, v.w};
-    __builtin_nontemporal_store(t, reinterpret_cast<d4v*>(p));
-  } else {
-    *p = v;
-  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -125,7 +84,7 @@ __device__ __forceinline__ void st_stream4(double4* p, double4 v)
 // 1 - 1.5 %: all of those keep the plain gather.
 __host__ __device__ constexpr bool sf_coop_variant(bool cohe, bool lub, int lpa, bool tp, int ntp)
 {
-  return SF_COOP_GATHER && lpa == 1 && (ntp == 1 || ntp == 2) && ((cohe && lub) || (!cohe && !lub && !tp));
+  return lpa == 1 && (ntp == 1 || ntp == 2) && ((cohe && lub) || (!cohe && !lub && !tp));
 }
 __device__ __forceinline__ void swap32(unsigned& a, unsigned& b)
 {
@@ -172,35 +131,10 @@ __device__ __forceinline__ double4 coop_load(const double4* arr, const int ja, c
   return double4{a.x, a.y, b.x, b.y};
 }
 
-// Persistent tiles (k_substep_persist, PERS): what a wave reads about its atom before it can start the neighbour loop -- the
-// atom's three records, its row count and its first two list words.  The persistent kernel requests these for the wave's NEXT
-// tile when the neighbour loop of the current tile is over (the loop's register sets are dead by then), so that they arrive
-// while the current tile's fixes, integration and stores run.
-struct TilePre {
-  double4 x, v, w;
-  int nn_all, w_first, w_second;
-  int q;        // lane 0: what the XCD's head word returned (the wave's tile after the next one is 2 x resident + q)
-  int* head;
-  const DemPtrs* Pe;       // the kernel arguments as the epilogue reads them (see substep_particle)
-  const StepParams* Se;
-};
-template <bool NT_LD>
-__device__ __forceinline__ void tile_prefetch(const DemPtrs& P, const StepParams& S, const int i, TilePre& t)
-{
-  const size_t cap = (size_t)S.cap;
-  t.x = P.xr_in[i];
-  t.v = P.vm_in[i];
-  t.w = P.om_in[i];
-  t.nn_all = ld_stream<NT_LD>(&P.numneigh[i]);
-  t.w_first = ld_stream<NT_LD>(&P.neigh[i]);
-  t.w_second = ld_stream<NT_LD>(&(P.neigh + (S.nslots > 1 ? cap : 0))[i]);
-}
-
-template <int STYLE, bool COHE, bool LUB, bool LDS, int LPA, bool TP, int NTP, bool GS = false, bool PERS = false>
+template <int STYLE, bool COHE, bool LUB, bool LDS, int LPA, bool TP, int NTP, bool GS = false>
 __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepParams& S, const int i, const int q,
                                                  const double4* lx, const double4* lv, const double* lw,
-                                                 const unsigned long long gs_w = 0ull, const bool live = true,
-                                                 TilePre* pre = nullptr, const int i_next = -1)
+                                                 const unsigned long long gs_w = 0ull, const bool live = true)
 {
   // COOP: the records of a neighbour are read by lane pairs (l, l + 32) -- every lane of the wave walks the neighbour loop
   // to the wave's largest count, `live` = this lane holds an atom (the caller clamps i of the others to a valid one: they
@@ -220,24 +154,20 @@ __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepPara
   // (ghost slots: the gate normally waits behind the wave's own rows -- one round trip for both.  The wave whose own
   // records share a 128-byte line with the first ghost records must not pull that line in before the ghosts are there)
   bool gs_gated = false;
-#ifdef SF_GS_EXP_NOGATE   // (pricing arm of tests/ab_gs_arms.sh: not a correct hand-off)
-  gs_gated = true;
-#endif
   if (GS && S.gs_wait && !gs_gated && __ballot(i >= (S.nlocal & ~3))) {
     if (!gs_gate(P.gs_sync, P.flags, S.gs_seq, S.kstep)) return 0;
     gs_gated = true;
   }
-  // (PERS: requested one tile ago, see TilePre)
-  const double4 xi4 = PERS ? pre->x : P.xr_in[i];   // also a gather target of the neighbours: keep it cached
-  const double4 vi4 = PERS ? pre->v : P.vm_in[i];
-  const double4 wi4 = PERS ? pre->w : P.om_in[i];
+  const double4 xi4 = P.xr_in[i];   // also a gather target of the neighbours: keep it cached
+  const double4 vi4 = P.vm_in[i];
+  const double4 wi4 = P.om_in[i];
   const Vec3 xi = v3(xi4), vi = v3(vi4), wi = v3(wi4);
   const double radi = xi4.w, mi = vi4.w;
 
   Vec3 F = {0.0, 0.0, 0.0}, T = {0.0, 0.0, 0.0};
   const int mk = S.use_groups ? P.mask[i] : 1;   // group bits of this atom (bit 0 = all)
-  const int nn_all = PERS ? pre->nn_all : ld_stream<NT_LD>(&P.numneigh[i]);
-  const int nn = (COOP || PERS) ? (live ? nn_all : 0)   // (PERS: the lanes past the last atom stay for the wave's other tiles)
+  const int nn_all = ld_stream<NT_LD>(&P.numneigh[i]);
+  const int nn = COOP ? (live ? nn_all : 0)
                       : LPA == 1 ? nn_all : (nn_all > q ? (nn_all - q + LPA - 1) / LPA : 0);   // slots of this lane
   const double lub_cutsq = S.lub.cut_global * S.lub.cut_global;
 
@@ -253,10 +183,10 @@ __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepPara
   // bed against the two-wave form, cohesive 134.0 -> 120.6 us, lubricate/poly 176.8 -> 164.7 us; the kernel with both arms
   // spills at three waves and gains nothing (192.3 / 198.7 -> 191.9 us), it keeps two (profiles/r05_c5_README.md)
   constexpr bool LEAN = sf_lean_variant(COHE, LUB, LPA);
-  constexpr bool HIST_PF = SF_HIST_PREFETCH && !LEAN;
+  constexpr bool HIST_PF = !LEAN;
   struct Rec {
     double4 x, v, w;
-    Vec3 sh; // the pair's history as THIS side sees it (SF_HIST_PREFETCH)
+    Vec3 sh; // the pair's history as THIS side sees it (HIST_PF)
     int l;   // LDS: position of the neighbour in the staged tile
     bool vw; // v and w were requested
   };
@@ -337,8 +267,8 @@ __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepPara
   const int row1 = q + LPA < S.nslots ? q + LPA : S.nslots - 1;
   // (one lane per atom only: with several lanes per atom the two extra live registers spill)
   const bool ld0 = LPA == 1 || nn > 0, ld1 = LPA == 1 || nn > 1;
-  const int w_first = PERS ? pre->w_first : ld0 ? ld_stream<NT_LD>(&(P.neigh + (size_t)q * cap)[i]) : 0;
-  const int w_second = PERS ? pre->w_second : ld1 ? ld_stream<NT_LD>(&(P.neigh + (size_t)row1 * cap)[i]) : 0;
+  const int w_first = ld0 ? ld_stream<NT_LD>(&(P.neigh + (size_t)q * cap)[i]) : 0;
+  const int w_second = ld1 ? ld_stream<NT_LD>(&(P.neigh + (size_t)row1 * cap)[i]) : 0;
   int jraw_n1 = nn > 0 ? w_first : 0;
   int jraw_n2 = nn > 1 ? w_second : 0;
   // One history copy per contact: a partner-side slot (kOwnBit clear) reads the owner's previous value from the
@@ -394,10 +324,7 @@ __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepPara
     jraw_n1 = jraw_n2;
     if (s + 2 < nn) jraw_n2 = ld_stream<NT_LD>(&(nrow + (size_t)(2 * LPA) * cap)[i]);
     else if (COOP) jraw_n2 = 0;   // (a lane beyond its count keeps loading for its partner: word 0 = atom 0, no bits)
-    if (more) {
-      bool reuse = false;
-      if (!reuse) fetch(jraw_n1, sl + LPA, nxt);
-    }
+    if (more) fetch(jraw_n1, sl + LPA, nxt);
     double4 xj4 = cur.x, vj4 = cur.v, wj4 = cur.w;
     if (LDS) {
       xj4 = lx[cur.l];
@@ -406,17 +333,7 @@ __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepPara
         wj4 = {lw[3 * cur.l], lw[3 * cur.l + 1], lw[3 * cur.l + 2], 0.0};
       }
     }
-    if (ROOTS && own) {
-      // periodic image of the root: the same x_root + shift the reference's forward_comm would have stored
-      // (a partner-side word never refers to an image: its code bits hold the owner's slot)
-      const int code = (jraw >> kIdxBits) & 31;
-      if (code != kNoShift) {
-        const int cz = code / 9, cy = (code - 9 * cz) / 3, cx = code - 9 * cz - 3 * cy;
-        xj4.x += (double)(cx - 1) * S.prd[0];
-        xj4.y += (double)(cy - 1) * S.prd[1];
-        xj4.z += (double)(cz - 1) * S.prd[2];
-      }
-    }
+    if (ROOTS && own) shift_to_image(xj4, jraw, S.prd);
     const Vec3 del = xi - v3(xj4);
     // (COOP: a lane beyond its own count is here for its partner's loads: no pair, nothing touches, nothing is stored)
     const double rsq = (COOP && s >= nn) ? 1.0e300 : dot(del, del);
@@ -448,17 +365,10 @@ __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepPara
         c.vr = vi - v3(vj4);
         c.wsum = {radi * wi.x + radj * wj4.x, radi * wi.y + radj * wj4.y, radi * wi.z + radj * wj4.z};
         const double mj = vj4.w;
-        c.overlap = radsum - c.r;
-#if SF_FAST_MATH
-        // meff = mi mj/(mi+mj) and reff = overlap radi radj/radsum share one reciprocal
-        const double msum = mi + mj;
-        const double inv = sf_rcp(msum * radsum);
-        c.meff = (mi * mj) * (radsum * inv);
-        c.reff = c.overlap * ((radi * radj) * (msum * inv));
-#else
-        c.meff = mi * mj / (mi + mj);
-        c.reff = (radsum - c.r) * radi * radj / radsum;
-#endif
+        const PairScales m = pair_scales(mi, mj, radi, radj, c.r);
+        c.overlap = m.overlap;
+        c.meff = m.meff;
+        c.reff = m.reff;
         if (S.freeze_bit) {   // pair_gran_hertzFix_history.cpp:188-189: a frozen partner is infinitely heavy
           if (wi4.w != 0.0) c.meff = mj;
           if (wj4.w != 0.0) c.meff = mi;
@@ -493,7 +403,7 @@ __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepPara
   // unrolled by two so that the prefetch ping-pongs between RA and RB without register copies
   SF_PH(1);
   int s = 0;
-  if constexpr (COOP && SF_UNROLL2 && !LEAN) {
+  if constexpr (COOP && !LEAN) {
     // (a counted loop in scalar registers: the largest count of the wave)
     for (; s + 1 < nn_wave; s += 2) {
       slot_body(s, RA, RB, true, true);
@@ -505,7 +415,7 @@ __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepPara
       slot_body(s, RA, RB, s + 1 < nn_wave, true);
       RA = RB;
     }
-  } else if constexpr (SF_UNROLL2 && !LEAN) {
+  } else if constexpr (!LEAN) {
     for (; s + 1 < nn; s += 2) {
       slot_body(s, RA, RB, true, true);
       slot_body(s + 1, RB, RA, s + 2 < nn, true);
@@ -518,7 +428,7 @@ __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepPara
     }
   }
   SF_PH(27);
-  if (COOP && !PERS && !live) return 1;   // (PERS: behind the prefetch of the next tile, below)
+  if (COOP && !live) return 1;
   if (LPA > 1) {
     // fixed tree: (q0 + q1) [+ (q2 + q3)] -- the same bits on every run
     for (int off = 1; off < LPA; off <<= 1) {
@@ -536,73 +446,59 @@ __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepPara
     }
   }
 
-  // (PERS: what follows reads the kernel arguments through a pointer the compiler cannot see through -- pre->ka, renewed per
-  // tile -- so that the ~100 scalar words only the fixes and the integration need are loaded where they are used, as in
-  // k_substep, instead of being kept live across the tile loop; the neighbour loop above keeps its scalars in registers)
-  const DemPtrs& PE = PERS ? *pre->Pe : P;
-  const StepParams& SE = PERS ? *pre->Se : S;
   // the rows the fixes and the integration read, requested TOGETHER here (one memory round trip instead of one per fix)
-  const bool use_fd = SE.have_fdrag && (mk & SE.fdrag_bit);   // fix_fluid_drag.cpp:145
+  const bool use_fd = S.have_fdrag && (mk & S.fdrag_bit);   // fix_fluid_drag.cpp:145
   Vec3 fd_in = {0.0, 0.0, 0.0}, xh_in = {0.0, 0.0, 0.0};
   unsigned wt_in = 0;
-  if (SE.have_fdrag) {
+  if (S.have_fdrag) {
     const size_t k = use_fd ? (size_t)i : 0;   // (a lane outside the group reads a valid element and drops it)
-    fd_in = {PE.fdrag[k], PE.fdrag[cap + k], PE.fdrag[2 * cap + k]};
+    fd_in = {P.fdrag[k], P.fdrag[cap + k], P.fdrag[2 * cap + k]};
   }
-  if (SE.mode == 0 && SE.have_nve)
-    xh_in = {ld_stream<NT_LD>(&PE.xhold[i]), ld_stream<NT_LD>(&PE.xhold[cap + i]), ld_stream<NT_LD>(&PE.xhold[2 * cap + i])};
-  if (SE.nwalls) wt_in = PE.wtouch[i];
-  // (PERS: the next tile's records and first words, requested BEHIND this tile's fix rows -- memory returns in order, the
-  // epilogue waits for its rows only -- and ahead of everything the epilogue computes and stores)
-  // (i_next: 64 x the next tile -- wave-uniform, so that nothing per lane crosses the neighbour loop for it; -1: no next tile)
-  if (PERS && SF_PERS_PREFETCH && i_next >= 0) {
-    if (SF_PERS_DYNAMIC && (threadIdx.x & 63) == 0) pre->q = atomicAdd(pre->head, 1);
-    const int in = i_next + (int)(threadIdx.x & 63);
-    tile_prefetch<NT_LD>(P, S, in < S.nlocal ? in : 0, *pre);
-  }
-  if (PERS && !live) return 1;
+  if (S.mode == 0 && S.have_nve)
+    xh_in = {ld_stream<NT_LD>(&P.xhold[i]), ld_stream<NT_LD>(&P.xhold[cap + i]), ld_stream<NT_LD>(&P.xhold[2 * cap + i])};
+  if (S.nwalls) wt_in = P.wtouch[i];
   // (fused forward pack: the send slots of a border atom, requested here so that they have arrived by the end)
   int txk0 = -1, txk1 = -1;
-  if (SE.tx_fused == 1 && (xi.x < SE.tx_xlo || xi.x >= SE.tx_xhi)) {
-    txk0 = PE.sendslot[0][i];
-    txk1 = PE.sendslot[1][i];
+  if (S.tx_fused == 1 && (xi.x < S.tx_xlo || xi.x >= S.tx_xhi)) {
+    txk0 = P.sendslot[0][i];
+    txk1 = P.sendslot[1][i];
   }
   // (brick driver: near an external face in any dimension)
-  const bool txb = SE.tx_fused == 2 && (xi.x < SE.tx_lo3[0] || xi.x >= SE.tx_hi3[0] || xi.y < SE.tx_lo3[1] ||
-                                       xi.y >= SE.tx_hi3[1] || xi.z < SE.tx_lo3[2] || xi.z >= SE.tx_hi3[2]);
+  const bool txb = S.tx_fused == 2 && (xi.x < S.tx_lo3[0] || xi.x >= S.tx_hi3[0] || xi.y < S.tx_lo3[1] ||
+                                      xi.y >= S.tx_hi3[1] || xi.z < S.tx_lo3[2] || xi.z >= S.tx_hi3[2]);
 
   // ---- post_force fixes: gravity -> fdrag -> walls; fix freeze zeroes what the fixes BEFORE it in the script (and
   // the pair styles) gave a frozen atom, the fixes after it still act ([3P] Modify::post_force runs them in script
   // order; the reference's bed cases have `fix 4 bottom freeze` followed by `fix ywall all wall/gran`).  Fa, Ta: what
   // the fixes after fix freeze add, in their order; a free atom sums everything in F, T as before ----
   Vec3 Fa = {0.0, 0.0, 0.0}, Ta = {0.0, 0.0, 0.0};
-  const bool any_post = SE.freeze_bit != 0;   // (wave-uniform: no fix freeze, nothing to keep apart)
-  if (SE.have_gravity && (mk & SE.grav_bit)) {
-    const Vec3 g = {mi * SE.gacc[0], mi * SE.gacc[1], mi * SE.gacc[2]};
+  const bool any_post = S.freeze_bit != 0;   // (wave-uniform: no fix freeze, nothing to keep apart)
+  if (S.have_gravity && (mk & S.grav_bit)) {
+    const Vec3 g = {mi * S.gacc[0], mi * S.gacc[1], mi * S.gacc[2]};
     F = F + g;
-    if (any_post && (SE.post_freeze & 1)) Fa = Fa + g;
+    if (any_post && (S.post_freeze & 1)) Fa = Fa + g;
   }
   if (use_fd) {
     Vec3 fd = fd_in;
-    if (SE.carrier_rho != 0.0) {
+    if (S.carrier_rho != 0.0) {
       const double rho = 3.0 * mi / (4.0 * kPiTypo * radi * radi * radi);
-      const Vec3 vo = {PE.vOld[i], PE.vOld[cap + i], PE.vOld[2 * cap + i]};
-      const Vec3 du = {PE.DuDt[i], PE.DuDt[cap + i], PE.DuDt[2 * cap + i]};
-      const double k = SE.carrier_rho / rho * 0.5 * mi;
-      fd.x += k * (du.x - (vi.x - vo.x) / SE.dt);
-      fd.y += k * (du.y - (vi.y - vo.y) / SE.dt);
-      fd.z += k * (du.z - (vi.z - vo.z) / SE.dt);
-      PE.vOld[i] = vi.x;
-      PE.vOld[cap + i] = vi.y;
-      PE.vOld[2 * cap + i] = vi.z;
+      const Vec3 vo = {P.vOld[i], P.vOld[cap + i], P.vOld[2 * cap + i]};
+      const Vec3 du = {P.DuDt[i], P.DuDt[cap + i], P.DuDt[2 * cap + i]};
+      const double k = S.carrier_rho / rho * 0.5 * mi;
+      fd.x += k * (du.x - (vi.x - vo.x) / S.dt);
+      fd.y += k * (du.y - (vi.y - vo.y) / S.dt);
+      fd.z += k * (du.z - (vi.z - vo.z) / S.dt);
+      P.vOld[i] = vi.x;
+      P.vOld[cap + i] = vi.y;
+      P.vOld[2 * cap + i] = vi.z;
     }
     F = F + fd;
-    if (any_post && (SE.post_freeze & 2)) Fa = Fa + fd;
+    if (any_post && (S.post_freeze & 2)) Fa = Fa + fd;
   }
-  if (SE.nwalls) {
+  if (S.nwalls) {
     unsigned wt = wt_in, wt_new = 0;
-    for (int w = 0; w < SE.nwalls; w++) {
-      const WallParams& W = SE.wall[w];
+    for (int w = 0; w < S.nwalls; w++) {
+      const WallParams& W = S.wall[w];
       if (!(mk & W.bit)) continue;   // fix_wall_granFix.cpp:290
       Vec3 dw = {0.0, 0.0, 0.0};
       Vec3 vw = {W.vwall[0], W.vwall[1], W.vwall[2]};   // 0 unless the wall wiggles or shears (:255-264)
@@ -633,16 +529,16 @@ __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepPara
       const size_t wb = ((size_t)(3 * w)) * cap + i;
       Vec3 sh = {0.0, 0.0, 0.0};
       if (wt & (1u << w)) {
-        sh.x = PE.wshear[wb];
-        sh.y = PE.wshear[wb + cap];
-        sh.z = PE.wshear[wb + 2 * cap];
+        sh.x = P.wshear[wb];
+        sh.y = P.wshear[wb + cap];
+        sh.z = P.wshear[wb + 2 * cap];
       }
       ContactOut o;
-      if (W.gp.style == 2) hertz_history_law(W.gp, SE.dt, shearupdate, c, sh, o);
-      else hooke_history_law(W.gp, SE.dt, shearupdate, c, sh, o);
-      PE.wshear[wb] = sh.x;
-      PE.wshear[wb + cap] = sh.y;
-      PE.wshear[wb + 2 * cap] = sh.z;
+      if (W.gp.style == 2) hertz_history_law(W.gp, S.dt, shearupdate, c, sh, o);
+      else hooke_history_law(W.gp, S.dt, shearupdate, c, sh, o);
+      P.wshear[wb] = sh.x;
+      P.wshear[wb + cap] = sh.y;
+      P.wshear[wb + 2 * cap] = sh.z;
       wt_new |= (1u << w);
       F = F + o.F;
       T = T - radi * o.tor;
@@ -651,38 +547,38 @@ __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepPara
         Ta = Ta - radi * o.tor;
       }
     }
-    if (wt_new != wt) PE.wtouch[i] = (unsigned char)wt_new;
+    if (wt_new != wt) P.wtouch[i] = (unsigned char)wt_new;
   }
 
   SF_PH(28);
   // ---- integrate: final(k) [+ initial(k+1)]  ([3P] FixNVESphere, dtf = dt/2, INERTIA = 0.4) ----
   // [3P] fix freeze: force and torque of the group's atoms are zeroed where the fix stands in the script
-  if (mk & SE.freeze_bit) {
+  if (mk & S.freeze_bit) {
     F = Fa;
     T = Ta;
   }
   Vec3 vn = vi, wn = wi, xn = xi;
   bool gs_trig = false;
-  if (SE.mode != 2 && SE.have_nve && (mk & SE.nve_bit)) {
-    const double dtf = 0.5 * SE.dt;
+  if (S.mode != 2 && S.have_nve && (mk & S.nve_bit)) {
+    const double dtf = 0.5 * S.dt;
     const double dtfm = dtf / mi;
     const double dtirot = (dtf / 0.4) / (radi * radi * mi);
     vn = vn + dtfm * F;
     wn = wn + dtirot * T;
-    if (SE.mode == 0) {
+    if (S.mode == 0) {
       vn = vn + dtfm * F;
-      xn = xn + SE.dt * vn;
+      xn = xn + S.dt * vn;
       wn = wn + dtirot * T;
       const double dx = xn.x - xh_in.x, dy = xn.y - xh_in.y, dz = xn.z - xh_in.z;
-      if (dx * dx + dy * dy + dz * dz > SE.trigger_sq) {
+      if (dx * dx + dy * dy + dz * dz > S.trigger_sq) {
         gs_trig = true;
-        atomicMin(&PE.flags[SE.trig_set], SE.kstep + SE.trig_add);
+        atomicMin(&P.flags[S.trig_set], S.kstep + S.trig_add);
         // (fused forward pack: no kernel will copy the trigger word into the vote headers before the exchange)
-        for (int p = 0; p < SE.tx_nhdr; p++) atomicMin(header_vote_ptr(PE.tx_sendbuf + PE.tx_hdr_off[p]), SE.kstep + SE.trig_add);
+        for (int p = 0; p < S.tx_nhdr; p++) atomicMin(header_vote_ptr(P.tx_sendbuf + P.tx_hdr_off[p]), S.kstep + S.trig_add);
       }
-      if (SE.margin_sq > 0.0) {
+      if (S.margin_sq > 0.0) {
         const double sx = xn.x - xi.x, sy = xn.y - xi.y, sz = xn.z - xi.z;
-        if (sx * sx + sy * sy + sz * sz > SE.margin_sq) PE.flags[F_MARGIN_FAIL] = 1;
+        if (sx * sx + sy * sy + sz * sz > S.margin_sq) P.flags[F_MARGIN_FAIL] = 1;
       }
     }
   }
@@ -690,39 +586,38 @@ __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepPara
   // k_forward_pack_fused would gather after this kernel
   if (txb) {
     for (int k = 0; k < kBrickSlots; k++) {
-      const int off = PE.bslot[(size_t)k * cap + i];
+      const int off = P.bslot[(size_t)k * cap + i];
       if (off < 0) break;
       const int bq = off >> kBlkShift;
       if (GS) {   // whole records into the neighbour's ghost slots (its x | v | omega arrays), in the neighbour's frame
         const size_t r = (size_t)(off & kBlkMask);
-        const double* sh = PE.tx_blkshift + 3 * bq;
-        gs_store(reinterpret_cast<double4*>(PE.tx_blkptr[bq]) + r, xn.x + sh[0], xn.y + sh[1], xn.z + sh[2], radi);
-        gs_store(reinterpret_cast<double4*>(PE.tx_blkptr[DemEngine::kMaxDirs + bq]) + r, vn.x, vn.y, vn.z, mi);
-        gs_store(reinterpret_cast<double4*>(PE.tx_blkptr[2 * DemEngine::kMaxDirs + bq]) + r, wn.x, wn.y, wn.z, wi4.w);
+        const double* sh = P.tx_blkshift + 3 * bq;
+        gs_store(reinterpret_cast<double4*>(P.tx_blkptr[bq]) + r, xn.x + sh[0], xn.y + sh[1], xn.z + sh[2], radi);
+        gs_store(reinterpret_cast<double4*>(P.tx_blkptr[DemEngine::kMaxDirs + bq]) + r, vn.x, vn.y, vn.z, mi);
+        gs_store(reinterpret_cast<double4*>(P.tx_blkptr[2 * DemEngine::kMaxDirs + bq]) + r, wn.x, wn.y, wn.z, wi4.w);
         continue;
       }
-      double* b = PE.tx_blkptr[bq] + (off & kBlkMask);
-      const size_t n = PE.tx_blkcnt[bq];   // (component-major block: [kForwardDoubles][n])
+      double* b = P.tx_blkptr[bq] + (off & kBlkMask);
+      const size_t n = P.tx_blkcnt[bq];   // (component-major block: [kForwardDoubles][n])
       b[0] = xn.x; b[n] = xn.y; b[2 * n] = xn.z;
       b[3 * n] = vn.x; b[4 * n] = vn.y; b[5 * n] = vn.z;
       b[6 * n] = wn.x; b[7 * n] = wn.y; b[8 * n] = wn.z;
     }
   }
-  if (SE.tx_fused == 1) {
+  if (S.tx_fused == 1) {
     auto put = [&](double* b, size_t n, double shift) {
       b[0] = xn.x + shift; b[n] = xn.y; b[2 * n] = xn.z;
       b[3 * n] = vn.x; b[4 * n] = vn.y; b[5 * n] = vn.z;
       b[6 * n] = wn.x; b[7 * n] = wn.y; b[8 * n] = wn.z;
     };
-    if (txk0 >= 0) put(PE.tx[0] + txk0, (size_t)SE.tx_n[0], SE.tx_shift[0]);
-    if (txk1 >= 0) put(PE.tx[1] + txk1, (size_t)SE.tx_n[1], SE.tx_shift[1]);
+    if (txk0 >= 0) put(P.tx[0] + txk0, (size_t)S.tx_n[0], S.tx_shift[0]);
+    if (txk1 >= 0) put(P.tx[1] + txk1, (size_t)S.tx_n[1], S.tx_shift[1]);
   }
   SF_PH(29);
-#if SF_ST_SHUFFLE
   // A 32-byte record per lane is two 16-byte stores at a 32-byte stride: each store instruction covers only half
   // of every cache line it touches.  When the whole wave holds consecutive atoms the halves are exchanged between
   // lanes so that each instruction writes 1 KiB of contiguous memory (lane l stores chunk l, then chunk 64 + l).
-  if (LPA == 1 && SE.part == 0 && __ballot(1) == ~0ull && (i & 63) == (int)(threadIdx.x & 63)) {
+  if (LPA == 1 && S.part == 0 && __ballot(1) == ~0ull && (i & 63) == (int)(threadIdx.x & 63)) {
     const int lane = threadIdx.x & 63;
     const int base = i - lane;
     // (the half-wave exchange of the gathers, backwards: the first store writes records 0..31 -- lane l their first 16
@@ -735,25 +630,17 @@ __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepPara
       *reinterpret_cast<double2*>(dst) = double2{a0, a1};
       *reinterpret_cast<double2*>(dst + 1024) = double2{a2, a3};
     };
-    store_shuffled(PE.xr_out, xn.x, xn.y, xn.z, radi);
-    store_shuffled(PE.vm_out, vn.x, vn.y, vn.z, mi);
-    store_shuffled(PE.om_out, wn.x, wn.y, wn.z, wi4.w);
-  } else
-#endif
-  {
-#if SF_NT_OUT
-    st_stream4<NT_ST>(&PE.xr_out[i], double4{xn.x, xn.y, xn.z, radi});
-    st_stream4<NT_ST>(&PE.vm_out[i], double4{vn.x, vn.y, vn.z, mi});
-    st_stream4<NT_ST>(&PE.om_out[i], double4{wn.x, wn.y, wn.z, wi4.w});
-#else
-    PE.xr_out[i] = {xn.x, xn.y, xn.z, radi};
-    PE.vm_out[i] = {vn.x, vn.y, vn.z, mi};
-    PE.om_out[i] = {wn.x, wn.y, wn.z, wi4.w};   // .w: frozen mark travels with the record
-#endif
+    store_shuffled(P.xr_out, xn.x, xn.y, xn.z, radi);
+    store_shuffled(P.vm_out, vn.x, vn.y, vn.z, mi);
+    store_shuffled(P.om_out, wn.x, wn.y, wn.z, wi4.w);
+  } else {
+    P.xr_out[i] = {xn.x, xn.y, xn.z, radi};
+    P.vm_out[i] = {vn.x, vn.y, vn.z, mi};
+    P.om_out[i] = {wn.x, wn.y, wn.z, wi4.w};   // .w: frozen mark travels with the record
   }
-  if (SE.mode != 0) {
-    PE.force[i] = {F.x, F.y, F.z, 0.0};
-    PE.torque[i] = {T.x, T.y, T.z, 0.0};
+  if (S.mode != 0) {
+    P.force[i] = {F.x, F.y, F.z, 0.0};
+    P.torque[i] = {T.x, T.y, T.z, 0.0};
   }
   SF_PH(30);
   return 1 | (txb ? 2 : 0) | (gs_trig ? 4 : 0);
@@ -763,11 +650,7 @@ __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepPara
 // (512 / 3, granule 8 = 168), and at two waves per SIMD it is 30 % slower (latency bound).  Asked for three waves the
 // compiler finds 167 without spilling.  With ONE of the cohesive / lubrication arms the lean loop (sf_lean_variant) fits
 // three waves (154 VGPRs / 168 with 12 bytes of scratch); with both arms the kernel needs 223 and stays at two.
-#ifdef SF_WAVES_PER_EU
-#define SF_SUBSTEP_ATTR __attribute__((amdgpu_waves_per_eu(SF_WAVES_PER_EU, SF_WAVES_PER_EU)))
-#else
 #define SF_SUBSTEP_ATTR __attribute__((amdgpu_waves_per_eu((COHE || LUB) && !sf_lean_variant(COHE, LUB, LPA) ? 1 : 3)))
-#endif
 // The dispatcher places block b on XCD b % 8 (each XCD has its own 4 MiB L2).  Atoms are sorted by bin, so giving
 // every XCD one contiguous range of blocks keeps an atom's neighbours in the L2 of the XCD that gathers them
 // (bijective remap, speed only: any placement gives the same result).
@@ -796,13 +679,11 @@ __global__ __launch_bounds__(256) SF_SUBSTEP_ATTR void k_substep(DemPtrs P, Step
   // first workgroup of the first XCD that has any)
   int gs_expected = 0;
   bool gs_poller = false;
-  // S.sweep_rev: every other sub-step walks each XCD's range from its END.  A sub-step touches ~3 x the 256 MB of the
-  // memory-side cache; sweeping always in the same direction it finds nothing of the previous sub-step there (cyclic
-  // access, LRU), sweeping back and forth the first third of what it needs is what the previous sub-step touched last.
+  // (xcd_remap 2: XCD x works on xcd_count[x] blocks from xcd_first[x]; 1: equal contiguous shares, xcd_contiguous_block())
   if (S.xcd_remap == 2) {
     const int xcd = bid & 7, loc = bid >> 3;
     if (loc >= S.xcd_count[xcd]) return;
-    bid = S.xcd_first[xcd] + (S.sweep_rev ? S.xcd_count[xcd] - 1 - loc : loc);
+    bid = S.xcd_first[xcd] + loc;
     if (GS) {
       const int lx = (int)(threadIdx.x & 7);
       gs_expected = S.xcd_count[lx];
@@ -811,9 +692,8 @@ __global__ __launch_bounds__(256) SF_SUBSTEP_ATTR void k_substep(DemPtrs P, Step
       gs_poller = loc == 0 && xcd == firstx;
     }
   } else {
-    const int nb = gridDim.x, xcd = bid & 7, q = nb >> 3, r = nb & 7;
-    const int cnt = xcd < r ? q + 1 : q, loc = bid >> 3;
-    if (S.xcd_remap) bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (S.sweep_rev ? cnt - 1 - loc : loc);
+    const int nb = gridDim.x, xcd = bid & 7, q = nb >> 3, r = nb & 7, loc = bid >> 3;
+    if (S.xcd_remap) bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
     if (GS) {
       const int lx = (int)(threadIdx.x & 7);
       gs_expected = lx < r ? q + 1 : q;
@@ -865,81 +745,6 @@ __global__ __launch_bounds__(256) SF_SUBSTEP_ATTR void k_substep(DemPtrs P, Step
     atomicMax(&P.xcd_time[xq + 32], (int)(wall_clock64() & 0x3fffffff));
 }
 
-
-#ifdef SF_EXP_PERSIST   // (pricing arm of round 6, tests/build_variant.sh pers -DSF_EXP_PERSIST=1: measured slower, not shipped --
-                        //  profiles/r06_README.md section 2)
-// ------------------------------------------------------------------------------------------------
-// Persistent tiles (round 6).  k_substep starts one wave per 64 atoms: every wave pays its own start -- kernel arguments,
-// the round trip for its atom's records, row count and first list words (3.7 us of a 33 us life) -- with nothing else of its
-// own to hide it behind.  Here the grid is the RESIDENT waves (three per SIMD), each walking tiles of 64 atoms of its XCD's
-// range: the first two by position, the others pulled from the XCD's head word (one returning atomic per tile, requested
-// two tiles ahead so that nothing ever waits for it).  When the neighbour loop of tile t is over -- its two prefetch
-// register sets are dead -- the wave requests tile t + 1's records, row count and first words (TilePre) and only then runs
-// tile t's fixes, integration and stores: the next tile's start-up round trip runs under the current tile's epilogue.
-// Same atoms, same operations in the same order as k_substep (tiles are the one-wave workgroups of the plain launch): the
-// results are bit-identical; which wave works on which tile never enters them.
-// One lane per atom, no ghost slots, no boundary / interior split.  Head words: two sets, the launch pulls from set
-// S.pq_par and clears the other one for the next launch (every launch does, before the trigger test: a launch that
-// returns at once still leaves the invariant in place).
-// ------------------------------------------------------------------------------------------------
-template <int STYLE, bool COHE, bool LUB, bool TP, int NTP>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((COHE && LUB) ? 1 : 3)))
-void k_substep_persist(DemPtrs P, StepParams S)
-{
-  const int lane = (int)threadIdx.x;
-  if (blockIdx.x < 8 && lane == 0) P.pq_head[((S.pq_par ^ 1) * 8 + (int)blockIdx.x) * 32] = 0;
-  if (__atomic_load_n(&P.flags[S.trig_test], __ATOMIC_RELAXED) < S.kstep) return;
-  const int xcd = (int)(blockIdx.x & 7), loc = (int)(blockIdx.x >> 3), nres = (int)(gridDim.x >> 3);
-  const int cnt = S.xcd_count[xcd], first = S.xcd_first[xcd];
-  if (loc >= cnt) return;
-  int* const head = P.pq_head + (S.pq_par * 8 + xcd) * 32;
-  const int xq = xcd * 64;
-  if (S.xcd_time && lane == 0 && loc == 0) atomicMin(&P.xcd_time[xq], (int)(wall_clock64() & 0x3fffffff));
-  constexpr bool NT_LD = NTP != 0;
-  // tile t of this XCD's range -> its first atom (wave-uniform); a lane past the last atom works on atom 0 and stores nothing
-  auto base_of = [&](const int t) { return (first + (S.sweep_rev ? cnt - 1 - t : t)) * 64; };
-  // tiles of this wave: loc, loc + nres (by position), then 2 nres + what the head word returns.  The pull for the tile
-  // after the next one is issued with the next tile's prefetch (substep_particle, behind the neighbour loop) and read here,
-  // one epilogue later: nothing waits for it
-  int t_next = loc + nres;                   // (wave-uniform: scalar registers)
-  int base = base_of(loc);
-  TilePre pre;
-  pre.head = head;
-  pre.q = 0;
-  {
-    const int i0 = base + lane;
-    tile_prefetch<NT_LD>(P, S, i0 < S.nlocal ? i0 : 0, pre);
-  }
-  // The epilogue of a tile reads the kernel arguments through a pointer the compiler cannot see through, renewed per tile:
-  // left alone it hoists every scalar load of the ~150 words of StepParams out of the tile loop, keeps them all live across
-  // it and spills (169 scalar + 37 vector registers).  The neighbour loop reads P and S directly: its scalars stay in
-  // registers across the tiles, as they do across the loop in k_substep (re-reading them inside the loop: +12 %).
-  typedef const char __attribute__((address_space(4))) * KernArg;
-  const KernArg ka0 = (KernArg)__builtin_amdgcn_kernarg_segment_ptr();
-  constexpr size_t kSOff = (sizeof(DemPtrs) + alignof(StepParams) - 1) / alignof(StepParams) * alignof(StepParams);
-  for (;;) {
-    KernArg ka = ka0;
-    asm volatile("" : "+s"(ka));
-    pre.Pe = (const DemPtrs*)(ka);
-    pre.Se = (const StepParams*)(ka + kSOff);
-    const int base_next = t_next < cnt ? base_of(t_next) : -1;
-    const int i = base + lane;
-    const bool live = i < S.nlocal;
-    substep_particle<STYLE, COHE, LUB, false, 1, TP, NTP, false, true>(P, S, live ? i : 0, 0, nullptr, nullptr, nullptr, 0ull,
-                                                                        live, &pre, base_next);
-    if (base_next < 0) break;
-    if (!SF_PERS_PREFETCH) {   // (pricing arm: the next tile's records requested when the current tile is done -- no overlap)
-      if (SF_PERS_DYNAMIC && lane == 0) pre.q = atomicAdd(head, 1);
-      const int in = base_next + lane;
-      tile_prefetch<NT_LD>(P, S, in < S.nlocal ? in : 0, pre);
-    }
-    base = base_next;
-    t_next = SF_PERS_DYNAMIC ? 2 * nres + __builtin_amdgcn_readfirstlane(pre.q) : t_next + nres;
-  }
-  if (S.xcd_time && lane == 0 && (loc & 7) == 0) atomicMax(&P.xcd_time[xq + 32], (int)(wall_clock64() & 0x3fffffff));
-}
-
-#endif
 
 // (the LDS-staged cell-bin kernel, k_substep_lds -- the same substep_particle on a tile's staged copy -- is in
 // sf_dem_lds_kernel.h)

@@ -263,12 +263,6 @@ __global__ __launch_bounds__(1024) void k_count_layers(const double4* xr, int nl
 __device__ __forceinline__ void key_runs(const unsigned key, int& head, int& len, int& rank)
 {
   const int lane = threadIdx.x & 63;
-#ifdef SF_EXP_NO_KEY_RUNS
-  head = lane;   // pricing / bisecting arm: every lane a run of its own
-  len = 1;
-  rank = 0;
-  return;
-#endif
   const unsigned long long act = __ballot(1);
   const unsigned prev = (unsigned)__shfl_up((int)key, 1, 64);
   const bool starts = lane == 0 || !((act >> (lane - 1)) & 1ull) || prev != key;
@@ -701,18 +695,13 @@ __device__ unsigned long long g_build_phase[8];
 // LC: the accepted candidates of the first sweep are parked in LDS ([B.M][128] words + [B.M][128] image-code bytes of
 // dynamic shared memory) instead of the scratch rows `cand`: a store to memory inside the candidate walk is waited for by
 // the wait of the NEXT record loads (one counter for loads and stores), so every step of the walk paid a write round trip
-#ifdef SF_EXP_BUILD_WAVES
-#define SF_BUILD_ATTR __attribute__((amdgpu_waves_per_eu(SF_EXP_BUILD_WAVES, SF_EXP_BUILD_WAVES)))
-#else
-#define SF_BUILD_ATTR
-#endif
 // ROWS: the row path (plain keys: B.lb_own) -- the cell-by-cell path of the tiled / LDS-staged orderings is an instantiation of
 // its own, so that neither carries the other's registers
 // (Measured and removed, profiles/r06_README.md section 3: two / four lanes per atom -- the rows of the stencil split into
 // contiguous blocks, the same list word for word in a chain of 1 / NL the length -- and a walk on single-precision shadow
 // records, one 16-byte load per candidate, eight candidates per step: neither shortens the kernel, at 100 k grains or at 1 M.)
 template <bool LC, bool ROWS = true>
-__global__ __launch_bounds__(128) SF_BUILD_ATTR void k_build_neigh(BuildParams B, const double4* xr, const int* tag,
+__global__ __launch_bounds__(128) void k_build_neigh(BuildParams B, const double4* xr, const int* tag,
                                                      const int* cellLS, const int* cellLE,
                                                      const int* cellGS, const int* cellGE,
                                                      const int* ghost_order, const int* numneigh_old,

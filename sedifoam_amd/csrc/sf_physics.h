@@ -142,6 +142,31 @@ struct ContactIn {
   double r, rinv;
 };
 
+// The mass and radius terms of a granular pair (pair_gran_hertzFix_history.cpp:183-187): overlap = radsum - r,
+// meff = mi mj / (mi + mj), reff = overlap radi radj / radsum.  One definition for the sub-step kernel and the thermo
+// virial, which must evaluate the same pair forces.  (The fix-freeze override of meff, :188-189, stays with the callers:
+// inside a helper the compiler no longer shapes that branch after the kernel around it.)
+struct PairScales {
+  double overlap, meff, reff;
+};
+__device__ __forceinline__ PairScales pair_scales(double mi, double mj, double radi, double radj, double r)
+{
+  const double radsum = radi + radj;
+  PairScales m;
+  m.overlap = radsum - r;
+#if SF_FAST_MATH
+  // meff and reff share one reciprocal
+  const double msum = mi + mj;
+  const double inv = sf_rcp(msum * radsum);
+  m.meff = (mi * mj) * (radsum * inv);
+  m.reff = m.overlap * ((radi * radj) * (msum * inv));
+#else
+  m.meff = mi * mj / (mi + mj);
+  m.reff = (radsum - r) * radi * radj / radsum;
+#endif
+  return m;
+}
+
 struct ContactOut {
   Vec3 F;          // force on the particle
   Vec3 tor;        // rinv * (del x fs); caller applies -radius

@@ -86,15 +86,7 @@ __global__ __launch_bounds__(kThermoBlock) void k_thermo_virial(DemPtrs P, StepP
       const int j = neigh_index(jraw, S.roots);
       const bool own = (jraw & kOwnBit) != 0;
       double4 xj4 = P.xr_in[j];
-      if (S.roots && own) {
-        const int code = (jraw >> kIdxBits) & 31;
-        if (code != kNoShift) {
-          const int cz = code / 9, cy = (code - 9 * cz) / 3, cx = code - 9 * cz - 3 * cy;
-          xj4.x += (double)(cx - 1) * S.prd[0];
-          xj4.y += (double)(cy - 1) * S.prd[1];
-          xj4.z += (double)(cz - 1) * S.prd[2];
-        }
-      }
+      if (S.roots && own) shift_to_image(xj4, jraw, S.prd);
       const Vec3 del = xi - tv3(xj4);
       const double rsq = dot(del, del);
       const double radj = xj4.w;
@@ -125,16 +117,10 @@ __global__ __launch_bounds__(kThermoBlock) void k_thermo_virial(DemPtrs P, StepP
         c.vr = vi - tv3(vj4);
         c.wsum = {radi * wi.x + radj * wj4.x, radi * wi.y + radj * wj4.y, radi * wi.z + radj * wj4.z};
         const double mj = vj4.w;
-        c.overlap = radsum - c.r;
-#if SF_FAST_MATH
-        const double msum = mi + mj;
-        const double inv = sf_rcp(msum * radsum);
-        c.meff = (mi * mj) * (radsum * inv);
-        c.reff = c.overlap * ((radi * radj) * (msum * inv));
-#else
-        c.meff = mi * mj / (mi + mj);
-        c.reff = (radsum - c.r) * radi * radj / radsum;
-#endif
+        const PairScales m = pair_scales(mi, mj, radi, radj, c.r);
+        c.overlap = m.overlap;
+        c.meff = m.meff;
+        c.reff = m.reff;
         if (S.freeze_bit) {   // pair_gran_hertzFix_history.cpp:188-189
           if (wi4.w != 0.0) c.meff = mj;
           if (wj4.w != 0.0) c.meff = mi;
