@@ -104,6 +104,18 @@ double sf_lammps_get_timestep(void *ptr);
 int sf_lammps_get_thermo(void *ptr, const char *keyword, double *out);
 /* kernel launches made for thermo lines so far (the virial pass and the reductions): 0 while no destination is open */
 int sf_lammps_thermo_launches(void *ptr, long long *launches);
+/* checkpoints (the script commands `write_restart FILE` / `read_restart FILE`; `*` in FILE = the current step).  A file
+ * holds box, units, timestep, step counter, groups, the owned atoms and their contact and wall shear history
+ * (sedifoam_amd/restart.py is the format's specification).  read_restart: before the box exists; pair_style, neighbor and
+ * the fixes are given again afterwards.  restart_launches: kernel launches made for checkpoints so far (0 for a run
+ * without them). */
+int sf_lammps_write_restart(void *ptr, const char *path);
+int sf_lammps_read_restart(void *ptr, const char *path);
+int sf_lammps_restart_launches(void *ptr, long long *launches);
+/* measurement (tools/restart_cost.py): timing_on brackets the pack of later checkpoints with events; out4 (may be NULL) =
+ * {GPU ms of the last pack, host ms until its pinned copy had landed, host ms until its file was renamed, 0}, after
+ * waiting for the writer */
+int sf_lammps_restart_cost(void *ptr, int timing_on, double *out4);
 /* library.h:61-63 (particle injection / removal; tag[] is double in the reference) */
 int sf_lammps_create_particle(void *ptr, int npAdd, const double *position, const double *tag,
                               double diameter, double rho, int type, const double *vel);
@@ -166,7 +178,8 @@ int sf_dem_need_rebuild(void *ptr);         /* 1 if any owned atom moved > skin/
 int sf_dem_substep_k(void *ptr, int last, int kstep);
 int sf_dem_batch_end(void *ptr, int first_k, int launched, int *trigger);
 int sf_dem_set_flag_buffer(void *ptr, void *dev_ints32);
-int sf_dem_setup(void *ptr);                /* first run's setup: forces with shearupdate = 0 */
+int sf_dem_setup(void *ptr);                /* a run's setup: list build + forces with shearupdate = 0; a list that exists
+                                             * keeps its shear history through it (the setup of a second run) */
 int sf_dem_rebuild_begin(void *ptr);        /* shear history -> partner tags; forget ghosts */
 int sf_dem_rebuild_sort(void *ptr);         /* pbc + sort owned atoms by bin (after migration) */
 int sf_dem_rebuild_finish(void *ptr);       /* periodic ghosts (y,z), bins, full list, history */

@@ -8,3 +8,4 @@ from ._lib import SfError, lib, exported_symbols  # noqa: F401
 from .lammps import Lammps  # noqa: F401
 from .cloud import enhancedCloud, dragModel, adjustLampTimestep  # noqa: F401
 from .dump import format_values, format_g  # noqa: F401
+from . import restart  # noqa: F401

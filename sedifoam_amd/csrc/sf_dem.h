@@ -592,6 +592,27 @@ class DemEngine {
   // sub-step of a piece -- are preceded by k_thermo_virial on the same inputs, which tallies that force evaluation's pair
   // virial into per-block partials.  A mode-1 launch behind a trigger runs again after the rebuild, and so does the pass.
   void set_thermo_virial(bool on) { thermo_virial_on_ = on; }
+  // ---- checkpoints (sf_restart.hip) ----
+  bool box_defined() const { return box_set_ || nlocal_ > 0; }
+  void set_nsteps(long long n)   // read_restart: thermo `Step`, the wall clocks and every schedule go on from it
+  {
+    nsteps_ = n;
+    predict_.external(n);
+  }
+  const std::map<std::string, int>& groups() const { return groups_; }
+  void set_groups(const std::map<std::string, int>& g) { groups_ = g; }
+  int nwalls() const { return nwalls_; }
+  // the owned atoms in ascending tag order, their touching contacts (once per contact, from the lower tag) and the wall
+  // rows, packed on the device and copied out; wall IDs are the caller's
+  size_t restart_pack_device(const char** blob, double* pack_ms);   // one block in a persistent device buffer
+  void restart_describe(struct RestartData& out) const;            // the header fields and the wall count
+  void restart_release();
+  void restart_partner_rows(int M);   // k_partner_tags on the live list into ptag_ / shear_[cur_ ^ 1] (sf_dem.hip)
+  // the atoms `keep` (positions in the file's order) become the owned atoms, their contacts partner rows that the first
+  // list build re-injects like those of a migrated atom
+  void restart_unpack(const struct RestartData& in, const std::vector<int>& keep);
+  void restart_wall_rows(int w, const std::vector<int>& tag, const std::vector<double>& shear3);
+  long long restart_launches() const { return restart_launches_; }
   const double* thermo_virial_partials() const { return thermo_vbuf_; }
   int thermo_virial_blocks() const { return thermo_vblocks_; }   // partial rows of the last pass (0: no owned atoms)
   long long thermo_virial_launches() const { return thermo_vlaunches_; }
@@ -648,6 +669,14 @@ private:
   int max_neigh_used_ = 0;
   int max_tag_ = 0;
   bool setup_done_ = false, have_list_ = false;
+  // read_restart: numneigh_ / ptag_ / shear_[hist_buf_] hold partner rows although no list was built yet
+  bool hist_rows_ = false;
+  bool old_rows() const { return have_list_ || hist_rows_; }
+  bool box_set_ = false;
+  long long restart_launches_ = 0, restart_order_ = -1;
+  void* rst_buf_[3] = {nullptr, nullptr, nullptr};   // counts, offsets, the block (grown, never shrunk)
+  size_t rst_cap_[3] = {0, 0, 0};
+  long long rst_hdr_[16];
   long long nbuilds_ = 0, nsteps_ = 0;
   double last_substep_ms_ = 0.0;
 

@@ -177,6 +177,7 @@ DemEngine::~DemEngine()
   if (sort_tmp_) (void)hipFree(sort_tmp_);
   if (own_flags_) (void)hipFree(own_flags_);
   if (count64_) (void)hipFree(count64_);
+  restart_release();
   if (h_flags_) (void)hipHostFree(h_flags_);
   if (ev0_) (void)hipEventDestroy(ev0_);
   if (ev1_) (void)hipEventDestroy(ev1_);
@@ -340,6 +341,7 @@ void DemEngine::set_box(const double lo[3], const double hi[3])
     boxlo_[k] = lo[k];
     boxhi_[k] = hi[k];
   }
+  box_set_ = true;
   for (int k = 0; k < 3; k++)
     if (!ext_[k]) {
       sublo_[k] = lo[k];
@@ -1314,6 +1316,13 @@ void DemEngine::compute_partner_tags()
         shear_[hist_buf_].as<double>(), nlocal_, cap_, max_neigh_used_, roots_ ? 1 : 0);
 }
 
+void DemEngine::restart_partner_rows(int M)
+{
+  k_partner_tags<<<div_up(nlocal_, 256), 256, 0, stream_>>>(neigh_.as<int>(), numneigh_.as<int>(), tag_.as<int>(),
+                                                            ptag_.as<int>(), shear_[cur_].as<double>(),
+                                                            shear_[cur_ ^ 1].as<double>(), nlocal_, cap_, M, roots_ ? 1 : 0);
+}
+
 void DemEngine::rebuild_begin()
 {
   if (!nlocal_ && !nghost_) return;
@@ -1393,12 +1402,12 @@ void DemEngine::permute_locals(const int* perm, int n_new, bool rows, const Rank
     g4(force_);
     g4(torque_);
   }
-  if (have_list_ && max_neigh_used_ > 0 && !rows) {
+  if (old_rows() && max_neigh_used_ > 0 && !rows) {
     // (the permutation itself becomes the index of the old rows: keep the array instead of copying it)
     if (perm == perm_alt_.as<int>()) std::swap(hist_perm_.ptr, perm_alt_.ptr);
     else SF_HIP(hipMemcpyAsync(hist_perm_.ptr, perm, sizeof(int) * n_new, hipMemcpyDeviceToDevice, stream_));
     hist_indirect_ = true;
-  } else if (have_list_ && max_neigh_used_ > 0) {
+  } else if (old_rows() && max_neigh_used_ > 0) {
     k_gather_rows<int><<<nb, 256, 0, stream_>>>(numneigh_old_.as<int>(), numneigh_.as<int>(), perm, n_new, 1, cap_);
     k_gather_rows<int><<<nb, 256, 0, stream_>>>(neigh_old_.as<int>(), ptag_.as<int>(), perm, n_new,
                                                 max_neigh_used_, cap_);
@@ -1713,33 +1722,33 @@ void DemEngine::bin_and_build()
     const bool quad = lc && !B.lb_ghost && !grid_.xslow && (lq == 2 || lq == 4 || lq == 8);
     if (quad && lq == 2)
       k_build_neigh_quad<2><<<div_up(nlocal_, 64), 128, lds_bytes / 2, stream_>>>(
-          B, xr_[cur_].as<double4>(), tag_.as<int>(), have_list_ ? numneigh_.as<int>() : nullptr, ptag_.as<int>(),
+          B, xr_[cur_].as<double4>(), tag_.as<int>(), old_rows() ? numneigh_.as<int>() : nullptr, ptag_.as<int>(),
           shear_[hist_buf_].as<double>(), new_words, numneigh_old_.as<int>(), shear_[hist_buf_ ^ 1].as<double>(), d_flags_,
           xhold_.as<double>());
     else if (quad && lq == 8)
       k_build_neigh_quad<8><<<div_up(nlocal_, 16), 128, lds_bytes / 8, stream_>>>(
-          B, xr_[cur_].as<double4>(), tag_.as<int>(), have_list_ ? numneigh_.as<int>() : nullptr, ptag_.as<int>(),
+          B, xr_[cur_].as<double4>(), tag_.as<int>(), old_rows() ? numneigh_.as<int>() : nullptr, ptag_.as<int>(),
           shear_[hist_buf_].as<double>(), new_words, numneigh_old_.as<int>(), shear_[hist_buf_ ^ 1].as<double>(), d_flags_,
           xhold_.as<double>());
     else if (quad)
       k_build_neigh_quad<4><<<div_up(nlocal_, 32), 128, lds_bytes / 4, stream_>>>(
-          B, xr_[cur_].as<double4>(), tag_.as<int>(), have_list_ ? numneigh_.as<int>() : nullptr, ptag_.as<int>(),
+          B, xr_[cur_].as<double4>(), tag_.as<int>(), old_rows() ? numneigh_.as<int>() : nullptr, ptag_.as<int>(),
           shear_[hist_buf_].as<double>(), new_words, numneigh_old_.as<int>(), shear_[hist_buf_ ^ 1].as<double>(), d_flags_,
           xhold_.as<double>());
     else if (lc)
       k_build_neigh<true><<<div_up(nlocal_, 128), 128, lds_bytes, stream_>>>(
           B, xr_[cur_].as<double4>(), tag_.as<int>(), cellLS, cellLE, cellGS, cellGE, perm_alt_.as<int>(),
-          have_list_ ? numneigh_.as<int>() : nullptr, ptag_.as<int>(), shear_[hist_buf_].as<double>(), new_words,
+          old_rows() ? numneigh_.as<int>() : nullptr, ptag_.as<int>(), shear_[hist_buf_].as<double>(), new_words,
           numneigh_old_.as<int>(), shear_[hist_buf_ ^ 1].as<double>(), d_flags_, nullptr, xhold_.as<double>());
     else if (!row_tables_)
       k_build_neigh<false, false><<<div_up(nlocal_, 128), 128, 0, stream_>>>(
           B, xr_[cur_].as<double4>(), tag_.as<int>(), cellLS, cellLE, cellGS, cellGE, perm_alt_.as<int>(),
-          have_list_ ? numneigh_.as<int>() : nullptr, ptag_.as<int>(), shear_[hist_buf_].as<double>(), new_words,
+          old_rows() ? numneigh_.as<int>() : nullptr, ptag_.as<int>(), shear_[hist_buf_].as<double>(), new_words,
           numneigh_old_.as<int>(), shear_[hist_buf_ ^ 1].as<double>(), d_flags_, neigh_old_.as<int>(), xhold_.as<double>());
     else
       k_build_neigh<false><<<div_up(nlocal_, 128), 128, 0, stream_>>>(
           B, xr_[cur_].as<double4>(), tag_.as<int>(), cellLS, cellLE, cellGS, cellGE, perm_alt_.as<int>(),
-          have_list_ ? numneigh_.as<int>() : nullptr, ptag_.as<int>(), shear_[hist_buf_].as<double>(), new_words,
+          old_rows() ? numneigh_.as<int>() : nullptr, ptag_.as<int>(), shear_[hist_buf_].as<double>(), new_words,
           numneigh_old_.as<int>(), shear_[hist_buf_ ^ 1].as<double>(), d_flags_, neigh_old_.as<int>(), xhold_.as<double>());
     // the host looks at the counts (overflow, widest row) while the partner-slot pass below is already running: it
     // needs nothing but the list, and a list that overflowed -- rare -- is built again and the pass repeated
@@ -1793,6 +1802,7 @@ void DemEngine::bin_and_build()
   static const int park_margin = getenv("SF_PARK_MARGIN") ? atoi(getenv("SF_PARK_MARGIN")) : 8;
   park_rows_ = std::max(1, std::min(M_, max_neigh_used_ + park_margin));
   have_list_ = true;   // (xhold, the positions the skin/2 check refers to, was stored by k_build_neigh)
+  hist_rows_ = false;  // (the rows read_restart left were re-injected into this list)
   nbuilds_++;
   if (xcd_auto_ && xcd_countdown_ == 0) xcd_countdown_ = 3;   // the third full launch on the new list is timed per XCD
 }
@@ -1931,7 +1941,8 @@ void DemEngine::setup()
 {
   if (!have_nve_ && nlocal_) { /* allowed: static atoms */ }
   if (!have_subdomain_) {
-    have_list_ = false;
+    // (a list that exists keeps its history through this rebuild, as FixShearHistory does across the setup of a second
+    // run [3P]; the first setup has none)
     rebuild();
   } else if (!have_list_)
     fail("sf_dem_setup on a decomposed domain: run the rebuild protocol (sf_dem_rebuild_*) first");

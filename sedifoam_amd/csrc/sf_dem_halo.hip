@@ -566,7 +566,7 @@ long long DemEngine::migrate_pack_dim(int dim, int side, double xshift, double* 
     MigratePtrs P = mig_ptrs(xr_[cur_], vm_[cur_], om_[cur_], tag_, type_, mask_, foamCpuId_, numneigh_, ptag_,
                              fdrag_, DuDt_, vOld_, wshear_, shear_[hist_buf_], wtouch_, extra_, nextra_);
     k_migrate_pack<<<div_up(n, 128), 128, 0, stream_>>>(list.as<int>(), n, xshift, P, cap_, nwalls_, mrec_,
-                                                        have_list_ ? 1 : 0, rec, buf, leave_.as<int>(), side + 1,
+                                                        old_rows() ? 1 : 0, rec, buf, leave_.as<int>(), side + 1,
                                                         d_flags_, dim);
   }
   migrate_leavers_ += n;

@@ -30,8 +30,12 @@ struct SfLammps {
   // thermo settings, destinations and the last line (sf_thermo.hip); opaque here like halo
   void* thermo = nullptr;
   void (*thermo_delete)(void*) = nullptr;
+  // the `restart` schedule, the fix IDs of the walls and the wall rows of a restart file (sf_restart.hip); opaque like halo
+  void* restart = nullptr;
+  void (*restart_delete)(void*) = nullptr;
   ~SfLammps()
   {
+    if (restart && restart_delete) restart_delete(restart);
     if (thermo && thermo_delete) thermo_delete(thermo);   // (closes the log and screen files)
     if (dumps && dumps_delete) dumps_delete(dumps);   // (drains the writer: the frames are in their files)
     if (halo && halo_delete) halo_delete(halo);

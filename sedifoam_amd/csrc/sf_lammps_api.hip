@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <map>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -16,6 +17,7 @@
 #include "../../include/sedifoam_amd.h"
 #include "sf_dump.h"
 #include "sf_handles.h"
+#include "sf_restart.h"
 #include "sf_roctx.h"
 #include "sf_thermo.h"
 
@@ -147,8 +149,9 @@ void advance(SfLammps& L, int n)
 // run).  Without a dump and without a thermo destination the run is not cut.
 void sf::run_steps(SfLammps& L, int n)
 {
-  const bool thermo = sf::thermo_active(L);
-  if (!sf::dump_active(L) && !thermo) {
+  const bool thermo = sf::thermo_active(L), rst = sf::restart_active(L);
+  sf::restart_run_begin(L);   // (wall rows of a restart file that no fix claimed are dropped here; host only)
+  if (!sf::dump_active(L) && !thermo && !rst) {
     L.eng.set_thermo_virial(false);
     advance(L, n);
     return;
@@ -165,8 +168,10 @@ void sf::run_steps(SfLammps& L, int n)
       next = std::min(next, sf::thermo_next_step(L, L.eng.nsteps()));
       sf::thermo_arm(L, next);   // (the pair virial of step `next`, when it has a line that shows pressure)
     }
+    if (rst) next = std::min(next, sf::restart_next_step(L, L.eng.nsteps()));
     advance(L, (int)(next - L.eng.nsteps()));
     sf::dump_write_due(L);
+    if (rst) sf::restart_write_due(L);
     if (thermo) sf::thermo_write_due(L);
   }
   if (thermo) sf::thermo_run_end(L);
@@ -239,6 +244,38 @@ void read_data(SfLammps& L, const std::string& path)
   }
   L.eng.create_atoms((int)tag.size(), x.data(), nullptr, nullptr, diam.data(), dens.data(), tag.data(),
                      type.data());
+}
+
+// [3P] read_restart: box, periodicity, units, timestep, step counter, groups and the owned atoms with their contact and
+// wall history (sf_restart.hip); pair_style, neighbor and the fixes are given again by the script.  On N ranks every
+// rank reads the file and keeps the atoms of its brick, like read_data.
+void read_restart(SfLammps& L, const std::string& path)
+{
+  if (L.eng.box_defined() || L.decomposed) sf::fail("Cannot read_restart after simulation box is defined");
+  sf::RestartData d;
+  sf::restart_file_read(path, d);
+  L.eng.set_periodic(d.periodic[0], d.periodic[1], d.periodic[2]);
+  L.eng.set_box(d.lo, d.hi);
+  sf::thermo_units(L, d.units_lj != 0);
+  std::map<std::string, int> groups;
+  for (const auto& g : d.groups) groups[g.first] = g.second;
+  if (!groups.count("all")) groups["all"] = 1;
+  L.eng.set_groups(groups);
+  L.eng.set_nsteps(d.step);
+  L.natoms = d.natoms;
+  const size_t n = (size_t)d.natoms;
+  std::vector<int> keep;
+  keep.reserve(n);
+  if (L.world_size > 1) {
+    decompose(L);
+    for (size_t i = 0; i < n; i++) {
+      const double x[3] = {d.x[i], d.x[n + i], d.x[2 * n + i]};
+      if (brick_owner(L, x) == L.world_rank) keep.push_back((int)i);
+    }
+  } else
+    for (size_t i = 0; i < n; i++) keep.push_back((int)i);
+  L.eng.restart_unpack(d, keep);
+  sf::restart_set_pending_walls(L, std::move(d.walls));
 }
 
 void cmd_pair_style(SfLammps& L, const std::vector<std::string>& w, size_t a)
@@ -359,6 +396,7 @@ void cmd_fix(SfLammps& L, const std::vector<std::string>& w)
       } else
         sf::fail("Illegal fix %s command", st.c_str());
     }
+    sf::restart_fix_wall(L, w[1], L.eng.nwalls() - 1);   // (the fix ID: a restart file's wall rows are matched by it)
   } else if (st == "freeze") {
     if (narg != 3) sf::fail("Illegal fix freeze command");   // [3P] fix_freeze.cpp
     L.eng.set_freeze(gb);
@@ -451,6 +489,15 @@ void command(SfLammps& L, const std::string& line)
     if (w.size() < 2) sf::fail("Illegal run command");
     run_steps(L, inum(w[1]));
     sf::dump_drain(L);   // (a script's run returns with its frames in their files)
+    sf::restart_drain(L);   // (... and its checkpoints)
+  } else if (c == "write_restart") {
+    if (w.size() != 2) sf::fail("Illegal write_restart command");
+    sf::write_restart_command(L, w[1]);
+  } else if (c == "read_restart") {
+    if (w.size() != 2) sf::fail("Illegal read_restart command");
+    read_restart(L, w[1]);
+  } else if (c == "restart") {
+    sf::restart_command(L, w);
   } else if (c == "dump") {
     sf::dump_command(L, w);
   } else if (c == "dump_modify") {
@@ -468,7 +515,7 @@ void command(SfLammps& L, const std::string& line)
     if (L.procgrid[0] && L.procgrid[1] && L.procgrid[2] &&
         L.procgrid[0] * L.procgrid[1] * L.procgrid[2] != L.world_size && L.world_size > 1)
       sf::fail("Specified processors != physical processors");   // [3P] Comm::set_proc_grid
-  } else if (c == "pair_coeff" || c == "atom_modify" || c == "restart" || c == "dimension") {
+  } else if (c == "pair_coeff" || c == "atom_modify" || c == "dimension") {
     // accepted, nothing to do on this path
   } else
     sf::fail("Unknown command: %s", c.c_str());
@@ -590,6 +637,7 @@ int sf_lammps_sync(void* ptr)
   SF_API_BEGIN
   SF_HIP(hipStreamSynchronize(H(ptr)->eng.stream()));
   sf::dump_drain(*H(ptr));   // (and the dump frames queued so far are in their files)
+  sf::restart_drain(*H(ptr));
   SF_API_END(0)
 }
 
@@ -692,6 +740,38 @@ int sf_lammps_thermo_launches(void* ptr, long long* launches)
   SF_API_BEGIN
   if (!launches) sf::fail("sf_lammps_thermo_launches: null argument");
   *launches = sf::thermo_launches(*H(ptr));
+  SF_API_END(0)
+}
+
+int sf_lammps_write_restart(void* ptr, const char* path)
+{
+  SF_API_BEGIN
+  if (!path) sf::fail("sf_lammps_write_restart: null path");
+  sf::write_restart_command(*H(ptr), path);
+  SF_API_END(0)
+}
+
+int sf_lammps_read_restart(void* ptr, const char* path)
+{
+  SF_API_BEGIN
+  if (!path) sf::fail("sf_lammps_read_restart: null path");
+  read_restart(*H(ptr), path);
+  SF_API_END(0)
+}
+
+int sf_lammps_restart_cost(void* ptr, int timing_on, double* out4)
+{
+  SF_API_BEGIN
+  sf::restart_timing(*H(ptr), timing_on != 0);
+  if (out4) sf::restart_last_cost(*H(ptr), out4);
+  SF_API_END(0)
+}
+
+int sf_lammps_restart_launches(void* ptr, long long* launches)
+{
+  SF_API_BEGIN
+  if (!launches) sf::fail("sf_lammps_restart_launches: null argument");
+  *launches = sf::restart_launches(*H(ptr));
   SF_API_END(0)
 }
 

@@ -20,6 +20,7 @@ bool thermo_command(SfLammps& L, const std::vector<std::string>& w);
 void thermo_echo(SfLammps& L, const std::string& line);
 // `units lj | si`: boltz and the default of `norm`
 void thermo_units(SfLammps& L, bool lj);
+bool thermo_units_lj(const SfLammps& L);   // (what a checkpoint records)
 // the `timestep` command, before dt changes: atime += (step - atimestep) dt ([3P] Update::update_time)
 void thermo_update_time(SfLammps& L);
 

@@ -494,6 +494,12 @@ void thermo_units(SfLammps& L, bool lj)
   if (!lj || L.thermo) ensure(L).lj = lj;
 }
 
+bool thermo_units_lj(const SfLammps& L)
+{
+  const Thermo* T = get(L);
+  return T ? T->lj : true;
+}
+
 void thermo_update_time(SfLammps& L)
 {
   // [3P] Update::update_time, what the timestep command does before dt changes (lammps_set_timestep does not)

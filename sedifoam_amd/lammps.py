@@ -118,6 +118,28 @@ class Lammps:
         check(self.L.sf_lammps_thermo_launches(self.ptr, C.byref(n)))
         return n.value
 
+    def write_restart(self, path):
+        """one checkpoint now (`write_restart FILE`; `*` = the current step); returns with the file complete"""
+        check(self.L.sf_lammps_write_restart(self.ptr, str(path).encode()))
+
+    def read_restart(self, path):
+        """box, units, timestep, step counter, groups, atoms and their contact / wall history from a checkpoint; before a
+        box exists, and pair_style / neighbor / the fixes are given again afterwards"""
+        check(self.L.sf_lammps_read_restart(self.ptr, str(path).encode()))
+
+    def restart_launches(self):
+        """kernel launches made for checkpoints so far"""
+        n = C.c_longlong()
+        check(self.L.sf_lammps_restart_launches(self.ptr, C.byref(n)))
+        return n.value
+
+    def restart_cost(self, timing=True):
+        """(GPU ms of the last checkpoint's pack, host ms until its pinned copy landed, host ms until its file was renamed);
+        timing=True makes later checkpoints time their pack (which then waits for it)"""
+        out = np.zeros(4)
+        check(self.L.sf_lammps_restart_cost(self.ptr, int(timing), _p(out)))
+        return tuple(out[:3])
+
     def create_particle(self, position, tag, diameter, rho, type_, vel):
         position = _f64(position).reshape(-1, 3)
         t = _f64(tag)
