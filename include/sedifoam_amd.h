@@ -112,6 +112,14 @@ int sf_lammps_thermo_launches(void *ptr, long long *launches);
 int sf_lammps_write_restart(void *ptr, const char *path);
 int sf_lammps_read_restart(void *ptr, const char *path);
 int sf_lammps_restart_launches(void *ptr, long long *launches);
+/* fix rigid/nve (bodies of spheres, one GPU).  set_molecule: the molecule IDs of the atoms with the given tags, for hosts
+ * that create atoms without a data file (what `read_data FILE fix ID NULL Molecules` reads); the row is made if no
+ * `fix ID all property/atom mol` did.  get_rigid: returns the number of bodies (max_bodies <= 0: the count alone, no
+ * array is touched); per body, ordered by the smallest tag it holds: natoms[1], masstotal[1], xcm[3], vcm[3], fcm[3],
+ * torque[3], angmom[3], omega[3], inertia[3] (principal moments), quat[4] (w x y z). */
+int sf_lammps_set_molecule(void *ptr, int n, const int *tags, const int *mol);
+int sf_lammps_get_rigid(void *ptr, int max_bodies, int *natoms, double *masstotal, double *xcm, double *vcm, double *fcm,
+                        double *torque, double *angmom, double *omega, double *inertia, double *quat);
 /* measurement (tools/restart_cost.py): timing_on brackets the pack of later checkpoints with events; out4 (may be NULL) =
  * {GPU ms of the last pack, host ms until its pinned copy had landed, host ms until its file was renamed, 0}, after
  * waiting for the writer */

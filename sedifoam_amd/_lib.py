@@ -107,6 +107,8 @@ _SIGS = {
     "sf_lammps_read_restart": (C.c_int, [vp, C.c_char_p]),
     "sf_lammps_restart_launches": (C.c_int, [vp, C.POINTER(C.c_longlong)]),
     "sf_lammps_restart_cost": (C.c_int, [vp, C.c_int, dp]),
+    "sf_lammps_set_molecule": (C.c_int, [vp, C.c_int, ip, ip]),
+    "sf_lammps_get_rigid": (C.c_int, [vp, C.c_int, ip] + [dp] * 9),
     "sf_lammps_create_particle": (C.c_int, [vp, C.c_int, dp, dp, C.c_double, C.c_double, C.c_int, dp]),
     "sf_lammps_delete_particle": (C.c_int, [vp, ip, C.c_int]),
     "sf_dem_create_atoms": (C.c_int, [vp, C.c_int, dp, dp, dp, dp, dp, ip, ip]),

@@ -175,6 +175,9 @@ struct DemPtrs {
   const int* tile_last;
   const int* stage_start;       // [ntiles+1] range of the tile in stage_idx
   const int* stage_idx;         // atom indices (owned or ghost) to stage, bin by bin
+  // fix rigid/nve (the RIGID instantiations only, sf_rigid.h): [cap] the mass the pair law sees -- the total mass of the
+  // atom's body, its own mass when it is in no body (pair_gran_hertzFix_history.cpp:72-86, 182-185)
+  const double* mbody;
 };
 
 // ghost slots: the flag / vote lines of the ranks (device copy, set up once per communicator)
@@ -616,6 +619,16 @@ class DemEngine {
   const double* thermo_virial_partials() const { return thermo_vbuf_; }
   int thermo_virial_blocks() const { return thermo_vblocks_; }   // partial rows of the last pass (0: no owned atoms)
   long long thermo_virial_launches() const { return thermo_vlaunches_; }
+  // ---- fix rigid/nve (sf_rigid.h, sf_rigid.hip): bodies of spheres, one domain ----
+  // bodystyle 0 single (the atoms of the group are one body), 1 group (one body per listed group), 2 molecule
+  void rigid_define(int bodystyle, int groupbit, const std::vector<int>& groupbits);
+  bool rigid_on() const { return rigid_ != nullptr; }
+  void rigid_molecule_row();                                        // fix ID all property/atom mol: zero-filled IDs
+  bool has_molecule() const { return have_molecule_; }
+  void rigid_set_molecule(int n, const int* tags, const int* mol);
+  void rigid_dirty();            // atoms changed behind the fix's back: the bodies are derived again before the next step
+  int rigid_nbody();
+  void rigid_get(int* natoms, double* fields);   // fields: [kBodyFields][nbody] (sf_rigid.h), bodies by smallest tag
 
  private:
   void ensure_capacity(size_t need);
@@ -883,6 +896,19 @@ private:
   int thermo_vblocks_ = 0;
   long long thermo_vlaunches_ = 0;
   void launch_thermo_virial(const DemPtrs& P, const StepParams& S);
+  struct RigidFix* rigid_ = nullptr;
+  DevArray rigid_rows_, rigid_rows_alt_;   // [kRigidRows][cap]: body, displace, mbody, molecule (allocated on first use)
+  bool have_molecule_ = false;
+  void rigid_release();
+  void rigid_rows_ensure();
+  void rigid_setup_bodies();
+  void rigid_map_rebuild();
+  void rigid_prepare(bool reduce);
+  void rigid_reduce(int kstep);
+  void rigid_integrate(int kstep, bool do_final, bool do_initial);
+  void rigid_writeback(int in_buf, int out_buf, int kstep, bool do_final, bool do_initial);
+  void rigid_after_setup_force(int in_buf);
+  void run_rigid(int nsteps);
 };
 
 // sf_sort.hip

@@ -15,6 +15,7 @@
 #include "sf_dem_rebuild.h"
 #include "sf_dem_io.h"
 #include "sf_dem_lds_kernel.h"
+#include "sf_rigid.h"
 #include "sf_roctx.h"
 #include "sf_thermo.h"
 
@@ -145,6 +146,7 @@ DemEngine::DemEngine()
 DemEngine::~DemEngine()
 {
   if (stream_) (void)hipStreamSynchronize(stream_);
+  rigid_release();
   for (DevArray* a : per_atom_) a->release();
   if (d_blkptr_) (void)hipFree(d_blkptr_);
 #ifdef SF_EXP_BUILD_PHASE
@@ -545,6 +547,7 @@ void DemEngine::set_velocity_group(int groupbit, double vx, double vy, double vz
   if (!nlocal_) return;
   k_set_velocity_group<<<div_up(nlocal_, 256), 256, 0, stream_>>>(vm_[cur_].as<double4>(), mask_.as<int>(), groupbit,
                                                                   nlocal_, vx, vy, vz);
+  rigid_dirty();
 }
 
 void DemEngine::add_wall(int dim, bool lo_null, double lo, bool hi_null, double hi, double kn, bool kt_null,
@@ -607,6 +610,7 @@ void DemEngine::set_velocity_all(double vx, double vy, double vz)
 {
   if (!nlocal_) return;
   k_set_velocity<<<div_up(nlocal_, 256), 256, 0, stream_>>>(vm_[cur_].as<double4>(), nlocal_, vx, vy, vz);
+  rigid_dirty();
 }
 
 double DemEngine::max_radius() { return rmax_; }
@@ -818,6 +822,7 @@ DemPtrs DemEngine::ptrs(int in_buf) const
   P.tile_last = tile_tab_ ? tile_tab_ + tile_alloc_ : nullptr;
   P.stage_start = tile_tab_ ? tile_tab_ + 3 * tile_alloc_ : nullptr;
   P.stage_idx = stage_idx_;
+  P.mbody = rigid_rows_.ptr ? rigid_rows_.as<double>() + (size_t)RR_MBODY * cap_ : nullptr;
   return P;
 }
 
@@ -989,12 +994,15 @@ void DemEngine::launch_substep(int in_buf, int mode, int kstep, int part)
     return;
   }
   if (part == 2 && !nb_) return;   // (no event pair opened: the interior part then times itself)
+  if (rigid_ && (part || have_subdomain_ || lds_active_ || mode == 0))
+    fail("fix rigid/nve needs the whole system on one GPU (one rank, no decomposed domain, no LDS-staged kernel)");
   DemPtrs P = ptrs(in_buf);
   StepParams S = step_params(mode, kstep);
   // thermo output: the pair virial of this force evaluation, from the inputs it reads (an overlapped sub-step: before its
   // boundary part, which the driver queues behind the ghosts of the previous exchange; before the interior part only
   // when there is no boundary part)
-  if (thermo_virial_on_ && mode != 0 && (part != 1 || !nb_)) launch_thermo_virial(P, S);
+  // (never with fix rigid/nve, whose every launch is mode 1: the thermo keywords that need the virial are refused with it)
+  if (thermo_virial_on_ && mode != 0 && !rigid_ && (part != 1 || !nb_)) launch_thermo_virial(P, S);
   // ghost slots: every stepping launch of a decomposed engine reads the ghosts of other GPUs from the area of its number's
   // parity and (mode 0) writes its border records into the neighbours' area of the next parity; the setup evaluation
   // (mode 2) runs on the ghosts the border exchange has just put into the record arrays
@@ -1098,7 +1106,7 @@ void DemEngine::launch_substep(int in_buf, int mode, int kstep, int part)
     if (nwork <= 0) return;
     // lanes per atom: small systems are latency bound (one lane walks all ~12 neighbours).  Measured: 10 k atoms
     // 17.3 -> 10.5 us per sub-step with 4 lanes, while at 100 k (1.5 waves per SIMD already) more lanes are slower
-    const int lpa = lanes_per_atom(nwork);
+    const int lpa = rigid_ ? 1 : lanes_per_atom(nwork);   // (the RIGID instantiations: one lane per atom)
     const long long lanes = (long long)nwork * lpa;
     // one wave per workgroup: the dispatcher then balances single waves (a 256-thread workgroup holds its CU slots
     // until its slowest wave is done); measured 207.0 -> 203.2 us per sub-step at 1 M atoms, never slower below
@@ -1131,7 +1139,8 @@ void DemEngine::launch_substep(int in_buf, int mode, int kstep, int part)
       grid = dim3((unsigned)(8 * most));
     }
     stamp_last_grid_ = grid.x;
-    switch (gran_.style) {
+    if (rigid_) launch_substep_rigid(gran_.style, cohe, lub, grid, block, stream_, P, S);
+    else switch (gran_.style) {
       case 2: launch_substep_style<2>(cohe, lub, lpa, touch_prefetch_, nt_policy_, grid, block, stream_, P, S); break;
       case 3:
       case 1: launch_substep_style<1>(cohe, lub, lpa, touch_prefetch_, nt_policy_, grid, block, stream_, P, S); break;
@@ -1382,6 +1391,7 @@ void DemEngine::permute_locals(const int* perm, int n_new, bool rows, const Rank
     add_rows(vOld_, vOld_alt_, 3);
   }
   if (nextra_) add_rows(extra_, extra_alt_, nextra_);
+  if (rigid_rows_.ptr) add_rows(rigid_rows_, rigid_rows_alt_, kRigidRows);   // body, displace, mbody, molecule
   if (nwalls_) {
     add_rows(wshear_, tmpd_, 3 * nwalls_);
     J.sb = wtouch_.as<unsigned char>();
@@ -1920,6 +1930,7 @@ void DemEngine::rebuild()
   rebuild_begin();
   rebuild_sort();
   rebuild_finish();
+  if (rigid_) rigid_map_rebuild();   // (the body -> atom map follows the new atom order)
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1940,6 +1951,10 @@ double DemEngine::local_particle_volume()
 void DemEngine::setup()
 {
   if (!have_nve_ && nlocal_) { /* allowed: static atoms */ }
+  if (rigid_) {
+    if (have_subdomain_) fail("fix rigid/nve needs the whole system on one GPU (one rank, no decomposed domain)");
+    if (rigid_->dirty) rigid_setup_bodies();   // (before the sort: the per-atom rows then travel with their atoms)
+  }
   if (!have_subdomain_) {
     // (a list that exists keeps its history through this rebuild, as FixShearHistory does across the setup of a second
     // run [3P]; the first setup has none)
@@ -1973,6 +1988,7 @@ void DemEngine::setup()
   reset_flag(F_TRIGGER, INT_MAX);
   wall_time_origin_ = nsteps_;   // FixWallGranFix::init, fix_wall_granFix.cpp:181
   launch_substep(cur_, 2, 0);
+  if (rigid_) rigid_after_setup_force(cur_);
   launch_ghost_forward(cur_ ^ 1, 0);
   cur_ ^= 1;
   measure_list();   // (the setup evaluation has set the touch bits of the first list)
@@ -2161,6 +2177,10 @@ void DemEngine::run(int nsteps)
   if (!setup_done_) setup();
   if (nsteps <= 0) return;
   // (an engine the SCRIPT decomposed never gets here: sf_lammps_step routes it to sf_slab_step, sf_lammps_api.hip)
+  if (rigid_) {
+    run_rigid(nsteps);
+    return;
+  }
   if (have_subdomain_) fail("DemEngine::run on a sub-domain set by sf_dem_set_subdomain / sf_slab_init / sf_brick_init: step it with sf_slab_step (or the sf_dem_* pieces)");
   run_base_step_ = nsteps_;
   choose_kernel();

@@ -16,6 +16,7 @@
 
 #include "sf_dem.h"
 #include "sf_dem_gs.h"
+#include "sf_rigid.h"
 
 namespace sf {
 
@@ -1208,6 +1209,9 @@ void DemEngine::create_particles(int np, const double* pos, const double* tag, d
     up(DuDt_, z.data(), sizeof(double) * np, sizeof(double) * ((size_t)c * cap_ + nlocal_));
     up(vOld_, z.data(), sizeof(double) * np, sizeof(double) * ((size_t)c * cap_ + nlocal_));
   }
+  // (fix property/atom mol without a rigid fix: the new atoms are in no molecule; with the fix the script layer refuses)
+  for (int r = 0; rigid_rows_.ptr && r < kRigidRows; r++)
+    up(rigid_rows_, z.data(), sizeof(double) * np, sizeof(double) * ((size_t)r * cap_ + nlocal_));
   std::vector<unsigned char> zb(np, 0);
   up(wtouch_, zb.data(), np, nlocal_);
   for (int r = 0; r < nextra_; r++) {   // client rows: the value registered for atoms that did not exist before

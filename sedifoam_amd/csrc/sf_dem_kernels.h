@@ -131,7 +131,9 @@ __device__ __forceinline__ double4 coop_load(const double4* arr, const int ja, c
   return double4{a.x, a.y, b.x, b.y};
 }
 
-template <int STYLE, bool COHE, bool LUB, bool LDS, int LPA, bool TP, int NTP, bool GS = false>
+// RIGID (fix rigid/nve, sf_rigid.h): the pair law sees the mass of an atom's body on both sides (DemPtrs::mbody), force and
+// torque are stored and nothing is integrated -- the bodies and the free atoms are advanced by the kernels of sf_rigid.hip.
+template <int STYLE, bool COHE, bool LUB, bool LDS, int LPA, bool TP, int NTP, bool GS = false, bool RIGID = false>
 __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepParams& S, const int i, const int q,
                                                  const double4* lx, const double4* lv, const double* lw,
                                                  const unsigned long long gs_w = 0ull, const bool live = true)
@@ -163,6 +165,8 @@ __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepPara
   const double4 wi4 = P.om_in[i];
   const Vec3 xi = v3(xi4), vi = v3(vi4), wi = v3(wi4);
   const double radi = xi4.w, mi = vi4.w;
+  double mi_pair = mi;   // (walls, cohesion, lubrication, gravity and fdrag keep the atom's own mass)
+  if (RIGID) mi_pair = P.mbody[i];
 
   Vec3 F = {0.0, 0.0, 0.0}, T = {0.0, 0.0, 0.0};
   const int mk = S.use_groups ? P.mask[i] : 1;   // group bits of this atom (bit 0 = all)
@@ -364,14 +368,15 @@ __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepPara
         }
         c.vr = vi - v3(vj4);
         c.wsum = {radi * wi.x + radj * wj4.x, radi * wi.y + radj * wj4.y, radi * wi.z + radj * wj4.z};
-        const double mj = vj4.w;
-        const PairScales m = pair_scales(mi, mj, radi, radj, c.r);
+        double mj = vj4.w;
+        if (RIGID) mj = P.mbody[cur.l];
+        const PairScales m = pair_scales(mi_pair, mj, radi, radj, c.r);
         c.overlap = m.overlap;
         c.meff = m.meff;
         c.reff = m.reff;
         if (S.freeze_bit) {   // pair_gran_hertzFix_history.cpp:188-189: a frozen partner is infinitely heavy
           if (wi4.w != 0.0) c.meff = mj;
-          if (wj4.w != 0.0) c.meff = mi;
+          if (wj4.w != 0.0) c.meff = mi_pair;
         }
         ContactOut o;
         gran_history_law<STYLE>(S.gran, S.dt, shearupdate, c, sh, o);
@@ -559,7 +564,7 @@ __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepPara
   }
   Vec3 vn = vi, wn = wi, xn = xi;
   bool gs_trig = false;
-  if (S.mode != 2 && S.have_nve && (mk & S.nve_bit)) {
+  if (!RIGID && S.mode != 2 && S.have_nve && (mk & S.nve_bit)) {
     const double dtf = 0.5 * S.dt;
     const double dtfm = dtf / mi;
     const double dtirot = (dtf / 0.4) / (radi * radi * mi);
@@ -617,7 +622,9 @@ __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepPara
   // A 32-byte record per lane is two 16-byte stores at a 32-byte stride: each store instruction covers only half
   // of every cache line it touches.  When the whole wave holds consecutive atoms the halves are exchanged between
   // lanes so that each instruction writes 1 KiB of contiguous memory (lane l stores chunk l, then chunk 64 + l).
-  if (LPA == 1 && S.part == 0 && __ballot(1) == ~0ull && (i & 63) == (int)(threadIdx.x & 63)) {
+  if (RIGID) {
+    // (the records of the next sub-step are written by k_rigid_writeback)
+  } else if (LPA == 1 && S.part == 0 && __ballot(1) == ~0ull && (i & 63) == (int)(threadIdx.x & 63)) {
     const int lane = threadIdx.x & 63;
     const int base = i - lane;
     // (the half-wave exchange of the gathers, backwards: the first store writes records 0..31 -- lane l their first 16
@@ -663,7 +670,7 @@ __device__ __forceinline__ int xcd_contiguous_block()
 // TP: v and omega of a neighbour are requested with its x only when the pair touched one sub-step ago (a bed that
 // lists many more neighbours than it touches: -11 % in the loose disordered bed), or always (a bed whose listed
 // neighbours nearly all touch: the bookkeeping of the former costs 4 % there)
-template <int STYLE, bool COHE, bool LUB, int LPA, bool TP, int NTP, bool GS = false>
+template <int STYLE, bool COHE, bool LUB, int LPA, bool TP, int NTP, bool GS = false, bool RIGID = false>
 __global__ __launch_bounds__(256) SF_SUBSTEP_ATTR void k_substep(DemPtrs P, StepParams S)
 {
   // a previous sub-step of this batch moved an atom beyond skin/2: the list is stale, do nothing
@@ -739,7 +746,7 @@ __global__ __launch_bounds__(256) SF_SUBSTEP_ATTR void k_substep(DemPtrs P, Step
     if (__ballot(ran == 0)) return;   // (stopped at the gate -- the whole wave did: the gate is a wave-level decision)
     if (S.mode == 0) gs_done(P, S, (ran & 2) != 0, (ran & 4) != 0, gs_poller, gs_expected);
   } else {
-    substep_particle<STYLE, COHE, LUB, false, LPA, TP, NTP>(P, S, i, q, nullptr, nullptr, nullptr, 0ull, live);
+    substep_particle<STYLE, COHE, LUB, false, LPA, TP, NTP, false, RIGID>(P, S, i, q, nullptr, nullptr, nullptr, 0ull, live);
   }
   if (S.xcd_time && threadIdx.x == 0 && ((blockIdx.x >> 3) & 7) == 0)
     atomicMax(&P.xcd_time[xq + 32], (int)(wall_clock64() & 0x3fffffff));
@@ -749,7 +756,8 @@ __global__ __launch_bounds__(256) SF_SUBSTEP_ATTR void k_substep(DemPtrs P, Step
 // (the LDS-staged cell-bin kernel, k_substep_lds -- the same substep_particle on a tile's staged copy -- is in
 // sf_dem_lds_kernel.h)
 // first half-kick of a run with the forces stored by the previous run's last sub-step
-__global__ __launch_bounds__(256) void k_initial_integrate(double4* xr, double4* vm, double4* om,
+// (the plain kernels of this header are static: sf_rigid.hip includes it too, for its instantiations of k_substep)
+__global__ __launch_bounds__(256) static void k_initial_integrate(double4* xr, double4* vm, double4* om,
                                                            const double4* force, const double4* torque,
                                                            const double* xhold, int* flags, int nlocal,
                                                            size_t cap, double dt, double trigger_sq,
@@ -780,7 +788,7 @@ __global__ __launch_bounds__(256) void k_initial_integrate(double4* xr, double4*
 }
 
 // [3P] Comm::forward_comm for images owned by this GPU: ghost = root atom + accumulated shift
-__global__ __launch_bounds__(256) void k_ghost_forward(double4* xr, double4* vm, double4* om,
+__global__ __launch_bounds__(256) static void k_ghost_forward(double4* xr, double4* vm, double4* om,
                                                        const int* gsrc, const double* gshift,
                                                        int nlocal, int nghost, size_t cap,
                                                        const int* flags, int kstep, int trig_word, int phase)
@@ -806,7 +814,7 @@ __global__ __launch_bounds__(256) void k_ghost_forward(double4* xr, double4* vm,
 // overlapped halo: an owned atom is a BOUNDARY atom when the forward halo sends it or when its list holds a ghost
 // whose root is owned by another GPU (gsrc < 0, or an image of such a ghost); everything else is interior and
 // never reads what the halo exchange writes.
-__global__ __launch_bounds__(256) void k_mark_boundary(const int* neigh, const int* numneigh, const int* gsrc,
+__global__ __launch_bounds__(256) static void k_mark_boundary(const int* neigh, const int* numneigh, const int* gsrc,
                                                        const int* send0, int n0, const int* send1, int n1,
                                                        int nlocal, size_t cap, unsigned char* isb, int phase,
                                                        int roots)

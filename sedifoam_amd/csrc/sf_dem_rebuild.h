@@ -332,7 +332,7 @@ __global__ __launch_bounds__(256) void k_gather4(double4* dst, const double4* sr
 
 // every per-atom array of the owned atoms in one launch: dst[i] = src[perm[i]] (DemEngine::permute_locals)
 struct PermuteJobs {
-  static constexpr int kRowArrays = 5;
+  static constexpr int kRowArrays = 6;
   const double4* s4[3];
   double4* d4[3];
   const int* si[4];

@@ -2,6 +2,7 @@
 #pragma once
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "sf_dem.h"
 
@@ -20,6 +21,7 @@ struct SfLammps {
   bool decomposed = false;       // the bricks were set up by the script path (sf_brick_init behind read_data)
   bool pending_rebuild = false;  // lammps_create_particle / lammps_delete_particle: next_reneighbor (library.cpp:482-486)
   long long natoms = -1;         // atom->natoms (library.cpp:94-98): set by read_data, create / delete particle
+  std::vector<std::string> property_atom_ids;   // IDs of `fix ID all property/atom mol` (read_data ... fix ID NULL Molecules)
   // RCCL communicator + events of the C++ halo loop (sf_halo_rccl.hip); opaque here so that only that file
   // sees the RCCL headers
   void* halo = nullptr;

@@ -18,6 +18,7 @@
 #include "sf_dump.h"
 #include "sf_handles.h"
 #include "sf_restart.h"
+#include "sf_rigid.h"
 #include "sf_roctx.h"
 #include "sf_thermo.h"
 
@@ -150,6 +151,9 @@ void advance(SfLammps& L, int n)
 void sf::run_steps(SfLammps& L, int n)
 {
   const bool thermo = sf::thermo_active(L), rst = sf::restart_active(L);
+  if (thermo && L.eng.rigid_on() && sf::thermo_needs_dof(L))
+    sf::fail("thermo output with temp / press / ke / etotal / p** needs the degrees of freedom of the rigid bodies, which "
+             "fix rigid/nve does not keep yet: use thermo_style custom without them, or -screen none -log none");
   sf::restart_run_begin(L);   // (wall rows of a restart file that no fix claimed are dropped here; host only)
   if (!sf::dump_active(L) && !thermo && !rst) {
     L.eng.set_thermo_virial(false);
@@ -187,7 +191,7 @@ void recount_atoms(SfLammps& L)
   L.natoms = (long long)n;
 }
 
-void read_data(SfLammps& L, const std::string& path)
+void read_data(SfLammps& L, const std::string& path, bool molecules = false)
 {
   // [3P] read_data for atom_style sphere: "N atoms", "lo hi xlo xhi" ..., section "Atoms":
   // id type diameter density x y z   (e.g. cases/auto-testing/test-cases/xiaocase3/IC_uniform.in)
@@ -197,9 +201,9 @@ void read_data(SfLammps& L, const std::string& path)
   std::getline(f, line);  // title
   long natoms = -1;
   double lo[3] = {0, 0, 0}, hi[3] = {1, 1, 1};
-  bool in_atoms = false;
+  bool in_atoms = false, in_mol = false, in_skip = false;
   std::vector<double> x, diam, dens;
-  std::vector<int> tag, type;
+  std::vector<int> tag, type, mol_tag, mol_id;
   while (std::getline(f, line)) {
     std::vector<std::string> w = split(line);
     if (w.empty()) continue;
@@ -211,7 +215,26 @@ void read_data(SfLammps& L, const std::string& path)
       else if (w[0] == "Atoms") in_atoms = true;
       continue;
     }
-    if (w[0] == "Velocities") break;
+    // sections after Atoms: `Molecules` (tag mol per line: read_data FILE fix ID NULL Molecules) is read when asked for,
+    // anything else ends the part of the file this engine reads, as before
+    if (w[0] == "Molecules" && molecules) {
+      in_mol = true;
+      in_skip = false;
+      continue;
+    }
+    if (w[0] == "Velocities") {
+      if (!molecules) break;
+      in_skip = true;
+      in_mol = false;
+      continue;
+    }
+    if (in_skip) continue;
+    if (in_mol) {
+      if (w.size() < 2) sf::fail("Incorrect format of the Molecules section in data file");
+      mol_tag.push_back(inum(w[0]));
+      mol_id.push_back(inum(w[1]));
+      continue;
+    }
     if (w.size() < 7) sf::fail("Incorrect atom format in data file");
     tag.push_back(inum(w[0]));
     type.push_back(inum(w[1]));
@@ -244,6 +267,11 @@ void read_data(SfLammps& L, const std::string& path)
   }
   L.eng.create_atoms((int)tag.size(), x.data(), nullptr, nullptr, diam.data(), dens.data(), tag.data(),
                      type.data());
+  if (molecules) {
+    if (L.world_size > 1) sf::fail("read_data ... fix ID NULL Molecules: one rank only (fix rigid/nve)");
+    if (mol_tag.size() != tag.size()) sf::fail("read_data: the Molecules section does not list every atom");
+    L.eng.rigid_set_molecule((int)mol_tag.size(), mol_tag.data(), mol_id.data());
+  }
 }
 
 // [3P] read_restart: box, periodicity, units, timestep, step counter, groups and the owned atoms with their contact and
@@ -400,6 +428,37 @@ void cmd_fix(SfLammps& L, const std::vector<std::string>& w)
   } else if (st == "freeze") {
     if (narg != 3) sf::fail("Illegal fix freeze command");   // [3P] fix_freeze.cpp
     L.eng.set_freeze(gb);
+  } else if (st == "property/atom") {
+    // [3P] fix ID all property/atom mol: a per-atom molecule ID, zero until read_data ... fix ID NULL Molecules or
+    // sf_lammps_set_molecule fills it
+    if (narg != 4 || w[4] != "mol") sf::fail("fix property/atom: only `fix ID all property/atom mol` is supported");
+    if (gb != 1) sf::fail("fix property/atom mol: the group must be all");
+    L.property_atom_ids.push_back(w[1]);
+    L.eng.rigid_molecule_row();
+  } else if (st == "rigid/nve") {
+    // [3P] fix ID group rigid/nve bodystyle args: single | group N g1 ... gN | molecule, no keywords
+    if (L.world_size > 1 || L.decomposed)
+      sf::fail("fix rigid/nve needs the whole system on one GPU (one rank, no decomposed domain)");
+    if (narg < 4) sf::fail("Illegal fix rigid/nve command");
+    const std::string& bs = w[4];
+    std::vector<int> gbits;
+    size_t iarg = 5;
+    int bodystyle = -1;
+    if (bs == "single") bodystyle = 0;
+    else if (bs == "molecule") bodystyle = 2;
+    else if (bs == "group") {
+      if (w.size() < 6) sf::fail("Illegal fix rigid/nve command");
+      const int ng = inum(w[5]);
+      if (ng < 1 || w.size() < 6 + (size_t)ng) sf::fail("Illegal fix rigid/nve command");
+      for (int k = 0; k < ng; k++) gbits.push_back(L.eng.group_bit(w[6 + k]));
+      iarg = 6 + (size_t)ng;
+      bodystyle = 1;
+    } else
+      sf::fail("fix rigid/nve: bodystyle %s is not supported (single, group, molecule are)", bs.c_str());
+    if (iarg < w.size())
+      sf::fail("fix rigid/nve: keyword %s is not supported (no langevin, temp, iso, aniso, x, y, z, couple, tparam, pchain, "
+               "dilate, force, torque, infile)", w[iarg].c_str());
+    L.eng.rigid_define(bodystyle, gb, gbits);
   } else
     sf::fail("Unknown fix style %s", st.c_str());
 }
@@ -454,7 +513,16 @@ void command(SfLammps& L, const std::string& line)
     L.eng.set_periodic(p[0], p[1], p[2]);
   } else if (c == "read_data") {
     if (w.size() < 2) sf::fail("Illegal read_data command");
-    read_data(L, w[1]);
+    bool molecules = false;
+    if (w.size() > 2) {
+      // [3P] read_data FILE fix ID NULL Molecules: the section `Molecules` belongs to fix ID (property/atom mol)
+      if (w.size() != 6 || w[2] != "fix" || w[4] != "NULL" || w[5] != "Molecules")
+        sf::fail("read_data: only `read_data FILE [fix ID NULL Molecules]` is supported");
+      if (std::find(L.property_atom_ids.begin(), L.property_atom_ids.end(), w[3]) == L.property_atom_ids.end())
+        sf::fail("Fix ID for read_data does not exist");
+      molecules = true;
+    }
+    read_data(L, w[1], molecules);
   } else if (c == "neighbor") {
     if (w.size() < 2) sf::fail("Illegal neighbor command");
     L.eng.set_skin(num(w[1]));
@@ -775,6 +843,45 @@ int sf_lammps_restart_launches(void* ptr, long long* launches)
   SF_API_END(0)
 }
 
+int sf_lammps_set_molecule(void* ptr, int n, const int* tags, const int* mol)
+{
+  SF_API_BEGIN
+  SfLammps* L = H(ptr);
+  if (L->world_size > 1 || L->decomposed) sf::fail("sf_lammps_set_molecule: one rank only (fix rigid/nve)");
+  L->eng.rigid_set_molecule(n, tags, mol);
+  SF_API_END(0)
+}
+
+int sf_lammps_get_rigid(void* ptr, int max_bodies, int* natoms, double* masstotal, double* xcm, double* vcm, double* fcm,
+                        double* torque, double* angmom, double* omega, double* inertia, double* quat)
+{
+  SF_API_BEGIN
+  DemEngine& e = H(ptr)->eng;
+  if (!e.rigid_on()) sf::fail("sf_lammps_get_rigid: no fix rigid/nve");
+  const int nb = e.rigid_nbody();
+  if (max_bodies <= 0) return nb;   // (the count alone)
+  if (nb > max_bodies) sf::fail("sf_lammps_get_rigid: %d bodies, room for %d", nb, max_bodies);
+  if (!natoms || !masstotal || !xcm || !vcm || !fcm || !torque || !angmom || !omega || !inertia || !quat)
+    sf::fail("sf_lammps_get_rigid: null argument");
+  std::vector<double> f((size_t)sf::kBodyFields * std::max(nb, 1));
+  e.rigid_get(natoms, f.data());
+  auto at = [&](int field, int b) { return f[(size_t)field * nb + b]; };
+  for (int b = 0; b < nb; b++) {
+    masstotal[b] = at(sf::BF_MASS, b);
+    for (int k = 0; k < 3; k++) {
+      xcm[3 * b + k] = at(sf::BF_XCM + k, b);
+      vcm[3 * b + k] = at(sf::BF_VCM + k, b);
+      fcm[3 * b + k] = at(sf::BF_FCM + k, b);
+      torque[3 * b + k] = at(sf::BF_TORQUE + k, b);
+      angmom[3 * b + k] = at(sf::BF_ANGMOM + k, b);
+      omega[3 * b + k] = at(sf::BF_OMEGA + k, b);
+      inertia[3 * b + k] = at(sf::BF_INERTIA + k, b);
+    }
+    for (int k = 0; k < 4; k++) quat[4 * b + k] = at(sf::BF_QUAT + k, b);
+  }
+  SF_API_END(nb)
+}
+
 double sf_lammps_get_timestep(void* ptr)
 {
   try {
@@ -790,6 +897,7 @@ int sf_lammps_create_particle(void* ptr, int npAdd, const double* position, cons
 {
   SF_API_BEGIN
   SfLammps* L = H(ptr);
+  if (L->eng.rigid_on()) sf::fail("lammps_create_particle: not while fix rigid/nve exists (its bodies are fixed sets of atoms)");
   L->eng.create_particles(npAdd, position, tag, diameter, rho, type, vel);
   if (L->decomposed) {   // library.cpp:470-473 (collective: every rank calls, possibly with npAdd = 0)
     recount_atoms(*L);
@@ -802,6 +910,7 @@ int sf_lammps_delete_particle(void* ptr, const int* deleteList, int nDelete)
 {
   SF_API_BEGIN
   SfLammps* L = H(ptr);
+  if (L->eng.rigid_on()) sf::fail("lammps_delete_particle: not while fix rigid/nve exists (its bodies are fixed sets of atoms)");
   L->eng.delete_particles(deleteList, nDelete);
   if (L->decomposed) {   // library.cpp:527-537: collective counts; every rank deletes the listed atoms it owns
     recount_atoms(*L);

@@ -27,6 +27,8 @@ void thermo_update_time(SfLammps& L);
 // ---- the run (sf::run_steps) ----
 // a destination is open: lines are computed and written.  The same answer on every rank (rank 0 alone writes).
 bool thermo_active(const SfLammps& L);
+// a line of the current style shows a quantity that counts degrees of freedom (temp, press, ke, etotal, p**)
+bool thermo_needs_dof(const SfLammps& L);
 // before the setup of a run: arm the pair virial of the setup force evaluation (first run only)
 void thermo_run_begin(SfLammps& L);
 // header and the line of the setup; `n` = steps of the run

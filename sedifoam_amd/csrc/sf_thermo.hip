@@ -586,6 +586,15 @@ bool thermo_active(const SfLammps& L)
   return T && (T->screen_named || T->log_named);
 }
 
+bool thermo_needs_dof(const SfLammps& L)
+{
+  const Thermo* T = get(L);
+  if (!T) return false;
+  for (int k : T->keys)
+    if (k == K_TEMP || k == K_PRESS || k == K_KE || k == K_ETOTAL || kKeys[k].virial) return true;
+  return false;
+}
+
 void thermo_run_begin(SfLammps& L)
 {
   Thermo& T = *get(L);

@@ -140,6 +140,24 @@ class Lammps:
         check(self.L.sf_lammps_restart_cost(self.ptr, int(timing), _p(out)))
         return tuple(out[:3])
 
+    def set_molecule(self, tags, mol):
+        """molecule IDs of the atoms with these tags (what `read_data FILE fix ID NULL Molecules` reads from a file)"""
+        t, m = _i32(tags), _i32(mol)
+        assert t.shape == m.shape
+        check(self.L.sf_lammps_set_molecule(self.ptr, t.shape[0], _p(t), _p(m)))
+
+    def rigid_bodies(self):
+        """the bodies of fix rigid/nve, ordered by the smallest tag they hold: natoms, masstotal, xcm, vcm, fcm, torque,
+        angmom, omega, inertia (principal moments), quat (w x y z)"""
+        nb = check(self.L.sf_lammps_get_rigid(self.ptr, 0, *([None] * 10)))
+        out = dict(natoms=np.zeros(nb, np.int32), masstotal=np.zeros(nb), xcm=np.zeros((nb, 3)), vcm=np.zeros((nb, 3)),
+                   fcm=np.zeros((nb, 3)), torque=np.zeros((nb, 3)), angmom=np.zeros((nb, 3)), omega=np.zeros((nb, 3)),
+                   inertia=np.zeros((nb, 3)), quat=np.zeros((nb, 4)))
+        if nb:
+            check(self.L.sf_lammps_get_rigid(self.ptr, nb, *[_p(out[k]) for k in (
+                "natoms", "masstotal", "xcm", "vcm", "fcm", "torque", "angmom", "omega", "inertia", "quat")]))
+        return out
+
     def create_particle(self, position, tag, diameter, rho, type_, vel):
         position = _f64(position).reshape(-1, 3)
         t = _f64(tag)
