@@ -17,6 +17,7 @@
 
 #include "../../include/sedifoam_amd.h"
 #include "sf_dump.h"
+#include "sf_env.h"
 #include "sf_handles.h"
 #include "sf_roctx.h"
 #include "sf_smooth.h"
@@ -775,7 +776,7 @@ class Cloud {
   // lanes that share one cell in the per-cell sums: by the mean number of particles per cell
   int lanes_per_cell(int n) const
   {
-    static const int env = getenv("SF_CELL_LANES") ? atoi(getenv("SF_CELL_LANES")) : 0;
+    static const int env = env_int("SF_CELL_LANES", 0);
     if (env) return env;
     const double per_cell = (double)n / (double)std::max(mesh_.ncells, 1);
     // measured at 37 particles per cell (1 M particles, 29x32x29 cells): k_calc_tc 130 / 46 / 96 us and

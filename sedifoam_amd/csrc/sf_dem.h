@@ -896,6 +896,15 @@ private:
   int thermo_vblocks_ = 0;
   long long thermo_vlaunches_ = 0;
   void launch_thermo_virial(const DemPtrs& P, const StepParams& S);
+  // the steps of launch_substep, in its order (gs: the ghost slots apply to this launch)
+  void substep_empty_rank(int mode, int kstep, bool gs);
+  void substep_ghost_slot_args(DemPtrs& P, StepParams& S);
+  void substep_split_args(StepParams& S, int kstep, int part) const;
+  void substep_forward_pack_args(StepParams& S, int mode, int part);
+  hipEvent_t substep_profile_open(int kstep, int part);
+  dim3 substep_grid(int mode, int part, StepParams& S, int& block, int& lpa);
+  void substep_dispatch(dim3 grid, int block, int lpa, const DemPtrs& P, const StepParams& S);
+  void substep_stamp_record(int mode, int part);
   struct RigidFix* rigid_ = nullptr;
   DevArray rigid_rows_, rigid_rows_alt_;   // [kRigidRows][cap]: body, displace, mbody, molecule (allocated on first use)
   bool have_molecule_ = false;

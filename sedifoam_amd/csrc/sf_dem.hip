@@ -11,9 +11,11 @@
 #include <cstdlib>
 #include <vector>
 
+#include "sf_dem_dispatch.h"
 #include "sf_dem_kernels.h"
 #include "sf_dem_rebuild.h"
 #include "sf_dem_io.h"
+#include "sf_env.h"
 #include "sf_dem_lds_kernel.h"
 #include "sf_rigid.h"
 #include "sf_roctx.h"
@@ -46,6 +48,10 @@ void fail(const char* fmt, ...)
   va_end(ap);
   throw Error(buf);
 }
+
+// (SF_DEBUG_HIST, SF_BLOCK: read at their first use, once per process)
+static bool debug_hist() { static const bool on = env_set("SF_DEBUG_HIST"); return on; }
+static int block_env() { static const int block = env_int("SF_BLOCK", 0); return block; }
 
 static double hertz_beta(double gamman)
 {
@@ -104,14 +110,14 @@ DemEngine::DemEngine()
   SF_HIP(hipEventCreate(&ev0_));
   SF_HIP(hipEventCreate(&ev1_));
   SF_HIP(hipEventCreateWithFlags(&ev_flags_, hipEventDisableTiming));
-  if (const char* e = getenv("SF_TILE")) opt_tile_ = atoi(e);
-  if (const char* e = getenv("SF_XCD_REMAP")) opt_xcd_remap_ = atoi(e);
+  opt_tile_ = env_int("SF_TILE", opt_tile_);
+  opt_xcd_remap_ = env_int("SF_XCD_REMAP", opt_xcd_remap_);
   SF_HIP(hipMalloc(&d_xcd_time_, sizeof(int) * 1024));
   SF_HIP(hipHostMalloc(&h_xcd_time_, sizeof(int) * 1024));
   for (int k = 0; k < 512; k++) h_xcd_time_[512 + k] = (k & 63) == 0 ? INT_MAX : 0;   // start: atomicMin, end: atomicMax
   SF_HIP(hipMemcpyAsync(d_xcd_time_ + 512, h_xcd_time_ + 512, sizeof(int) * 512, hipMemcpyHostToDevice, stream_));
-  if (const char* e = getenv("SF_XCD_BALANCE")) xcd_auto_ = atoi(e) != 0;
-  if (const char* e = getenv("SF_XCD_WEIGHTS")) {   // eight relative shares, comma separated: pins them
+  xcd_auto_ = env_flag("SF_XCD_BALANCE", xcd_auto_);
+  if (const char* e = env_str("SF_XCD_WEIGHTS")) {   // eight relative shares, comma separated: pins them
     double w[8];
     if (sscanf(e, "%lf,%lf,%lf,%lf,%lf,%lf,%lf,%lf", &w[0], &w[1], &w[2], &w[3], &w[4], &w[5], &w[6], &w[7]) == 8) {
       for (int x = 0; x < 8; x++) xcd_weight_[x] = w[x] > 0.0 ? w[x] : 1.0;
@@ -119,19 +125,16 @@ DemEngine::DemEngine()
       xcd_auto_ = false;
     }
   }
-  if (const char* e = getenv("SF_LDS")) opt_lds_ = atoi(e);
+  opt_lds_ = env_int("SF_LDS", opt_lds_);
   roots_ = !opt_lds_;
-  if (const char* e = getenv("SF_SUB")) {
-    opt_sub_ = std::max(1, atoi(e));
-    opt_sub_env_ = true;
-  }
-  if (const char* e = getenv("SF_HIST_COPIES")) hist_mode_env_ = atoi(e);
-  if (const char* e = getenv("SF_TOUCH_PREFETCH")) touch_prefetch_env_ = atoi(e);
-  if (const char* e = getenv("SF_TOUCH_FIRST")) touch_first_env_ = atoi(e);
-  if (const char* e = getenv("SF_NT_POLICY")) nt_policy_env_ = atoi(e);
-  if (const char* e = getenv("SF_LPA")) opt_lpa_ = atoi(e);
-  if (const char* e = getenv("SF_GHOST_FREE")) opt_ghost_free_ = atoi(e);
-  if (const char* e = getenv("SF_QUEUE_PREDICT")) predict_.on = atoi(e) != 0;
+  if ((opt_sub_env_ = env_override("SF_SUB", opt_sub_))) opt_sub_ = std::max(1, opt_sub_);
+  hist_mode_env_ = env_int("SF_HIST_COPIES", hist_mode_env_);
+  touch_prefetch_env_ = env_int("SF_TOUCH_PREFETCH", touch_prefetch_env_);
+  touch_first_env_ = env_int("SF_TOUCH_FIRST", touch_first_env_);
+  nt_policy_env_ = env_int("SF_NT_POLICY", nt_policy_env_);
+  opt_lpa_ = env_int("SF_LPA", opt_lpa_);
+  opt_ghost_free_ = env_int("SF_GHOST_FREE", opt_ghost_free_);
+  predict_.on = env_flag("SF_QUEUE_PREDICT", predict_.on);
   memset(&gran_, 0, sizeof(gran_));
   memset(&cohe_, 0, sizeof(cohe_));
   memset(&lub_, 0, sizeof(lub_));
@@ -721,7 +724,7 @@ void DemEngine::flags_copy_begin()
 
 void DemEngine::flags_copy_wait()
 {
-  static const bool spin = !(getenv("SF_FLAG_SPIN") && !atoi(getenv("SF_FLAG_SPIN")));
+  static const bool spin = env_flag("SF_FLAG_SPIN", true);
   const int* hf = h_flags_;
   bool seen = false;
   if (spin) {
@@ -753,7 +756,7 @@ void DemEngine::read_flags()
 void DemEngine::apply_xcd_sample()
 {
   xcd_sample_pending_ = false;
-  static const bool dbg = getenv("SF_DEBUG_XCD") != nullptr;
+  static const bool dbg = env_set("SF_DEBUG_XCD");
   int t0 = INT_MAX;
   for (int x = 0; x < 8; x++) t0 = std::min(t0, h_xcd_time_[64 * x]);
   double T[8], mean = 0.0;
@@ -886,44 +889,30 @@ StepParams DemEngine::step_params(int mode, int kstep) const
   return S;
 }
 
-template <int STYLE, int LPA, bool TP, int NTP, bool GS = false>
-static void launch_substep_lpa(bool cohe, bool lub, dim3 grid, int block, hipStream_t s, const DemPtrs& P,
-                               const StepParams& S)
+// The plain kernel's remaining axes, below pair_dispatch (sf_dem_dispatch.h): lanes per atom, TP (v, omega of the touching
+// neighbours prefetched: touch_prefetch_), ntp (non-temporal policy of the row streams, sf_dem_kernels.h) and GS
+template <int STYLE, bool COHE, bool LUB, bool GS>
+static void launch_plain(int lpa, bool tp, int ntp, dim3 grid, int block, hipStream_t s, const DemPtrs& P,
+                         const StepParams& S)
 {
-  if (cohe && lub) k_substep<STYLE, true, true, LPA, TP, NTP, GS><<<grid, block, 0, s>>>(P, S);
-  else if (cohe) k_substep<STYLE, true, false, LPA, TP, NTP, GS><<<grid, block, 0, s>>>(P, S);
-  else if (lub) k_substep<STYLE, false, true, LPA, true, NTP, GS><<<grid, block, 0, s>>>(P, S);   // (lubrication needs v, omega
-  else k_substep<STYLE, false, false, LPA, TP, NTP, GS><<<grid, block, 0, s>>>(P, S);            //  of every neighbour anyway)
-}
-
-template <int STYLE, int LPA, int NTP, bool GS = false>
-static void launch_substep_tp(bool cohe, bool lub, bool tp, dim3 grid, int block, hipStream_t s, const DemPtrs& P,
-                              const StepParams& S)
-{
-  if (lub) tp = true;   // one instantiation
-  tp ? launch_substep_lpa<STYLE, LPA, true, NTP, GS>(cohe, lub, grid, block, s, P, S)
-     : launch_substep_lpa<STYLE, LPA, false, NTP, GS>(cohe, lub, grid, block, s, P, S);
-}
-
-// ntp: non-temporal policy of the row streams (sf_dem_kernels.h); systems small enough for several lanes per atom
-// always fit the memory-side cache (policy 0)
-template <int STYLE>
-static void launch_substep_style(bool cohe, bool lub, int lpa, bool tp, int ntp, dim3 grid, int block, hipStream_t s,
-                                 const DemPtrs& P, const StepParams& S)
-{
-  // ghost slots (sf_halo_rccl.hip): the per-GPU share of a decomposed bed, nothing non-temporal -- one variant per lane count
-  if (S.gs_on) {
-    if (lpa == 4) launch_substep_tp<STYLE, 4, 0, true>(cohe, lub, tp, grid, block, s, P, S);
-    else if (lpa == 2) launch_substep_tp<STYLE, 2, 0, true>(cohe, lub, tp, grid, block, s, P, S);
-    else launch_substep_tp<STYLE, 1, 0, true>(cohe, lub, tp, grid, block, s, P, S);
-    return;
+  auto go = [&](auto lanes, auto policy) {
+    constexpr int LPA = decltype(lanes)::value, NTP = decltype(policy)::value;
+    // lubrication needs v, omega of every neighbour anyway: TP = true, one instantiation (with cohesion as well the
+    // TP = false one is compiled too, and never launched)
+    if constexpr (LUB && !COHE) k_substep<STYLE, COHE, LUB, LPA, true, NTP, GS><<<grid, block, 0, s>>>(P, S);
+    else if (tp || LUB) k_substep<STYLE, COHE, LUB, LPA, true, NTP, GS><<<grid, block, 0, s>>>(P, S);
+    else k_substep<STYLE, COHE, LUB, LPA, false, NTP, GS><<<grid, block, 0, s>>>(P, S);
+  };
+  // systems small enough for several lanes per atom always fit the memory-side cache (policy 0); ghost slots (sf_halo_rccl.hip)
+  // are the per-GPU share of a decomposed bed, nothing non-temporal: one variant per lane count
+  if (lpa == 4) go(int_c<4>{}, int_c<0>{});
+  else if (lpa == 2) go(int_c<2>{}, int_c<0>{});
+  else if (GS || ntp == 0) go(int_c<1>{}, int_c<0>{});
+  else if constexpr (!GS) {
+    if (ntp == 1) go(int_c<1>{}, int_c<1>{});
+    else if (ntp == 3) go(int_c<1>{}, int_c<3>{});
+    else go(int_c<1>{}, int_c<2>{});
   }
-  if (lpa == 4) launch_substep_tp<STYLE, 4, 0>(cohe, lub, tp, grid, block, s, P, S);
-  else if (lpa == 2) launch_substep_tp<STYLE, 2, 0>(cohe, lub, tp, grid, block, s, P, S);
-  else if (ntp == 0) launch_substep_tp<STYLE, 1, 0>(cohe, lub, tp, grid, block, s, P, S);
-  else if (ntp == 1) launch_substep_tp<STYLE, 1, 1>(cohe, lub, tp, grid, block, s, P, S);
-  else if (ntp == 3) launch_substep_tp<STYLE, 1, 3>(cohe, lub, tp, grid, block, s, P, S);
-  else launch_substep_tp<STYLE, 1, 2>(cohe, lub, tp, grid, block, s, P, S);
 }
 
 template <int STYLE, bool COHE, bool LUB>
@@ -935,18 +924,8 @@ static void launch_lds_one(dim3 grid, size_t lds, hipStream_t s, const DemPtrs& 
                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     granted = 160 * 1024;
   }
-  static const int threads = getenv("SF_LDS_THREADS") ? atoi(getenv("SF_LDS_THREADS")) : 256;
+  static const int threads = env_int("SF_LDS_THREADS", 256);
   k_substep_lds<STYLE, COHE, LUB><<<grid, threads, lds, s>>>(P, S);
-}
-
-template <int STYLE>
-static void launch_lds_style(bool cohe, bool lub, dim3 grid, size_t lds, hipStream_t s, const DemPtrs& P,
-                             const StepParams& S)
-{
-  if (cohe && lub) launch_lds_one<STYLE, true, true>(grid, lds, s, P, S);
-  else if (cohe) launch_lds_one<STYLE, true, false>(grid, lds, s, P, S);
-  else if (lub) launch_lds_one<STYLE, false, true>(grid, lds, s, P, S);
-  else launch_lds_one<STYLE, false, false>(grid, lds, s, P, S);
 }
 
 int DemEngine::lanes_per_atom(int nwork) const
@@ -978,81 +957,73 @@ void DemEngine::launch_thermo_virial(const DemPtrs& P, const StepParams& S)
   thermo_vlaunches_++;
 }
 
-void DemEngine::launch_substep(int in_buf, int mode, int kstep, int part)
+// ---- the steps of launch_substep, in its order ----
+// a rank without atoms: nothing to launch, but the bookkeeping of a launch
+void DemEngine::substep_empty_rank(int mode, int kstep, bool gs)
 {
-  if (!nlocal_) {
-    if (thermo_virial_on_ && mode != 0) {   // (thermo: a virial pass over no atoms, zero rows)
-      thermo_vblocks_ = 0;
-      thermo_vlaunches_++;
-    }
-    // (ghost slots: the other ranks wait for this one's flag whether it owns atoms or not)
-    if (gs_ready_ && brick_ && part == 0 && !lds_active_ && mode != 2) {
-      k_gs_idle<<<1, 64, 0, stream_>>>(d_gs_sync_, d_flags_, (int)gs_seq_, kstep, mode == 0 ? 1 : 0);
-      gs_seq_++;
-      tx_written_ = mode == 0;
-    }
-    return;
+  if (thermo_virial_on_ && mode != 0) {   // (thermo: a virial pass over no atoms, zero rows)
+    thermo_vblocks_ = 0;
+    thermo_vlaunches_++;
   }
-  if (part == 2 && !nb_) return;   // (no event pair opened: the interior part then times itself)
-  if (rigid_ && (part || have_subdomain_ || lds_active_ || mode == 0))
-    fail("fix rigid/nve needs the whole system on one GPU (one rank, no decomposed domain, no LDS-staged kernel)");
-  DemPtrs P = ptrs(in_buf);
-  StepParams S = step_params(mode, kstep);
-  // thermo output: the pair virial of this force evaluation, from the inputs it reads (an overlapped sub-step: before its
-  // boundary part, which the driver queues behind the ghosts of the previous exchange; before the interior part only
-  // when there is no boundary part)
-  // (never with fix rigid/nve, whose every launch is mode 1: the thermo keywords that need the virial are refused with it)
-  if (thermo_virial_on_ && mode != 0 && !rigid_ && (part != 1 || !nb_)) launch_thermo_virial(P, S);
-  // ghost slots: every stepping launch of a decomposed engine reads the ghosts of other GPUs from the area of its number's
-  // parity and (mode 0) writes its border records into the neighbours' area of the next parity; the setup evaluation
-  // (mode 2) runs on the ghosts the border exchange has just put into the record arrays
-  const bool gs = gs_ready_ && brick_ && part == 0 && !lds_active_ && mode != 2;
-  if (gs) {
-    // (before the launch takes its number: a refused launch must not leave a gap in the sequence the neighbours count)
-    static const int gs_block_env = getenv("SF_BLOCK") ? atoi(getenv("SF_BLOCK")) : 0;
-    if (gs_block_env && gs_block_env != 64)
-      fail("ghost slots: the hand-off at the end of the sub-step kernel is written for one-wave workgroups (SF_BLOCK)");
-    S.gs_on = 1;
-    S.gs_seq = (int)gs_seq_;
-    S.gs_wait = h_gs_sync_.world > 1 ? 1 : 0;   // (one rank that exchanges with itself: stream order is the hand-off)
-    S.gs_world = h_gs_sync_.world;
-    S.gs_rank = h_gs_sync_.rank;
-    P.gs_my_sync = h_gs_sync_.my_sync;
-    P.gs_sync = d_gs_sync_;
-    P.gs_count = d_gs_count_;
-    // (the records of the NEXT launch: the neighbours read them from the buffers of that launch's parity)
-    P.tx_blkptr = d_gsblk_ + (size_t)((gs_seq_ + 1) & 1) * 3 * kMaxDirs;
-    P.tx_blkshift = reinterpret_cast<const double*>(d_gsblk_ + 6 * (size_t)kMaxDirs);
+  if (gs) {   // (ghost slots: the other ranks wait for this one's flag whether it owns atoms or not)
+    k_gs_idle<<<1, 64, 0, stream_>>>(d_gs_sync_, d_flags_, (int)gs_seq_, kstep, mode == 0 ? 1 : 0);
     gs_seq_++;
+    tx_written_ = mode == 0;
   }
-  if (part) {
-    // overlapped halo: both parts of sub-step k test the vote published by the exchange of sub-step k-1; an
-    // interior trigger can only be voted one exchange later, hence "+1" (sub-step k+1 still runs everywhere)
-    S.part = part;
-    S.nb = nb_;
-    S.n_lo = n_lo_;
-    S.n_hi = n_hi_;
-    S.trig_test = F_VOTE0 + ((kstep + 1) & 1);
-    S.trig_set = F_TRIG_LOCAL;
-    S.trig_add = part == 1 ? 1 : 0;
-    const double half_margin = 0.5 * (lskin() - skin_);
-    S.margin_sq = half_margin * half_margin;
-  }
-  // the forward halo of the exchange that follows: written by the kernel that integrates the border atoms
+}
+
+// ghost slots: the launch takes its number in the sequence the neighbours count -- refused before that, if at all: a
+// refused launch must not leave a gap in the sequence
+void DemEngine::substep_ghost_slot_args(DemPtrs& P, StepParams& S)
+{
+  if (block_env() && block_env() != 64)
+    fail("ghost slots: the hand-off at the end of the sub-step kernel is written for one-wave workgroups (SF_BLOCK)");
+  S.gs_on = 1;
+  S.gs_seq = (int)gs_seq_;
+  S.gs_wait = h_gs_sync_.world > 1 ? 1 : 0;   // (one rank that exchanges with itself: stream order is the hand-off)
+  S.gs_world = h_gs_sync_.world;
+  S.gs_rank = h_gs_sync_.rank;
+  P.gs_my_sync = h_gs_sync_.my_sync;
+  P.gs_sync = d_gs_sync_;
+  P.gs_count = d_gs_count_;
+  // (the records of the NEXT launch: the neighbours read them from the buffers of that launch's parity)
+  P.tx_blkptr = d_gsblk_ + (size_t)((gs_seq_ + 1) & 1) * 3 * kMaxDirs;
+  P.tx_blkshift = reinterpret_cast<const double*>(d_gsblk_ + 6 * (size_t)kMaxDirs);
+  gs_seq_++;
+}
+
+// overlapped halo, the boundary part (2) or the interior part (1): both parts of sub-step k test the vote published by the
+// exchange of sub-step k-1; an interior trigger can only be voted one exchange later, hence "+1" (sub-step k+1 still runs everywhere)
+void DemEngine::substep_split_args(StepParams& S, int kstep, int part) const
+{
+  S.part = part;
+  S.nb = nb_;
+  S.n_lo = n_lo_;
+  S.n_hi = n_hi_;
+  S.trig_test = F_VOTE0 + ((kstep + 1) & 1);
+  S.trig_set = F_TRIG_LOCAL;
+  S.trig_add = part == 1 ? 1 : 0;
+  const double half_margin = 0.5 * (lskin() - skin_);
+  S.margin_sq = half_margin * half_margin;
+}
+
+// the forward halo of the exchange that follows: written by the kernel that integrates the border atoms
+void DemEngine::substep_forward_pack_args(StepParams& S, int mode, int part)
+{
   if (part != 1) tx_written_ = false;   // (the interior part sends nothing: what the boundary part wrote stands)
-  if (tx_ready_ && mode == 0 && !lds_active_) S.tx_nhdr = tx_direct_ ? 0 : tx_nhdr_;   // (direct: votes travel with the flags)
-  if (tx_ready_ && brick_ && mode == 0 && part == 0 && !lds_active_) {
+  if (!tx_ready_ || mode != 0 || lds_active_) return;
+  S.tx_nhdr = tx_direct_ ? 0 : tx_nhdr_;   // (direct: votes travel with the flags)
+  const double cut = cutneighmax() + skin_;   // (an atom is within skin/2 of where the send / border lists were made)
+  if (brick_ && part == 0) {
     S.tx_fused = 2;
     if (bslot_.cap != cap_) fail("launch_substep: the record-slot table has stride %zu, the engine %zu", bslot_.cap, cap_);
-    const double cut = cutneighmax() + skin_;   // (an atom is within skin/2 of where the send lists were made)
     for (int k = 0; k < 3; k++) {
       S.tx_lo3[k] = ext_[k] ? sublo_[k] + cut : -1.0e300;
       S.tx_hi3[k] = ext_[k] ? subhi_[k] - cut : 1.0e300;
     }
     tx_written_ = true;
-  } else if (tx_ready_ && mode == 0 && part != 1 && !lds_active_) {
+  } else if (part != 1) {
     S.tx_fused = 1;
-    const double cut = cutneighmax() + skin_;   // (an atom is within skin/2 of where the border lists were made)
     S.tx_xlo = sublo_[0] + cut;
     S.tx_xhi = subhi_[0] - cut;
     S.tx_shift[0] = tx_shift_[0];
@@ -1061,102 +1032,97 @@ void DemEngine::launch_substep(int in_buf, int mode, int kstep, int part)
     S.tx_n[1] = tx_n_[1];
     tx_written_ = true;
   }
-  const bool cohe = cohe_.enabled, lub = lub_.enabled;
-  // one event pair per sub-step: around the single kernel, or from the boundary part to the interior part
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+}
+
+// One event pair per sub-step: around the single kernel, or from the boundary part to the interior part.  Records the
+// opening event where this launch opens the pair; returns the closing event where this launch closes it, else null.
+hipEvent_t DemEngine::substep_profile_open(int kstep, int part)
+{
   // Sampled: an event pair around EVERY launch costs ~10 us per sub-step (the record is a system-scope release, the
   // caches are written back before the next kernel starts) -- 5 % at 1 M atoms, 50 % at 10 k.
-  static const int prof_stride = getenv("SF_PROF_STRIDE") ? std::max(1, atoi(getenv("SF_PROF_STRIDE"))) : 8;
-  if (profiling_ && kstep % prof_stride == 0) {
-    if (part != 1 || !prof_open_) {
-      if (prof_used_ + 2 > prof_ev_.size()) {
-        for (int k = 0; k < 2; k++) {
-          hipEvent_t e;
-          SF_HIP(hipEventCreate(&e));
-          prof_ev_.push_back(e);
-        }
-      }
-      if (prof_step_.size() < prof_ev_.size() / 2) prof_step_.resize(prof_ev_.size() / 2);
-      prof_step_[prof_used_ / 2] = kstep;
-      e0 = prof_ev_[prof_used_++];
-      e1 = prof_ev_[prof_used_++];
-      SF_HIP(hipEventRecord(e0, stream_));
-      prof_open_ = (part == 2);
-      if (part == 2) e1 = nullptr;
-    } else {
-      e1 = prof_ev_[prof_used_ - 1];
-      prof_open_ = false;
+  static const int prof_stride = std::max(1, env_int("SF_PROF_STRIDE", 8));
+  if (!profiling_ || kstep % prof_stride != 0) return nullptr;
+  if (part == 1 && prof_open_) {
+    prof_open_ = false;
+    return prof_ev_[prof_used_ - 1];
+  }
+  if (prof_used_ + 2 > prof_ev_.size()) {
+    for (int k = 0; k < 2; k++) {
+      hipEvent_t e;
+      SF_HIP(hipEventCreate(&e));
+      prof_ev_.push_back(e);
     }
   }
-  if (lds_active_ && part) fail("the LDS-staged kernel has no boundary/interior split (SF_LDS with the overlapped halo)");
-  if (lds_active_) {
-    // one workgroup per tile; LDS = staged x (32 B) + v (32 B) + omega (24 B) per atom of the extended tile
-    const dim3 grid(ntiles_);
-    const size_t lds = (size_t)stage_cap_ * 88;
-    switch (gran_.style) {
-      case 2: launch_lds_style<2>(cohe, lub, grid, lds, stream_, P, S); break;
-      case 3:   // (plain gran/hooke: the Hookean kernel, the law itself branches on GranParams::style)
-      case 1: launch_lds_style<1>(cohe, lub, grid, lds, stream_, P, S); break;
-      default: launch_lds_style<0>(cohe, lub, grid, lds, stream_, P, S); break;
-    }
-  } else {
-    // enough workgroups to cover the 256 CUs even for small beds (one atom per lane either way)
-    static const int block_env = getenv("SF_BLOCK") ? atoi(getenv("SF_BLOCK")) : 0;
-    const int nwork = part == 2 ? nb_ : (part == 1 ? n_hi_ - n_lo_ : nlocal_);
-    if (nwork <= 0) return;
-    // lanes per atom: small systems are latency bound (one lane walks all ~12 neighbours).  Measured: 10 k atoms
-    // 17.3 -> 10.5 us per sub-step with 4 lanes, while at 100 k (1.5 waves per SIMD already) more lanes are slower
-    const int lpa = rigid_ ? 1 : lanes_per_atom(nwork);   // (the RIGID instantiations: one lane per atom)
-    const long long lanes = (long long)nwork * lpa;
-    // one wave per workgroup: the dispatcher then balances single waves (a 256-thread workgroup holds its CU slots
-    // until its slowest wave is done); measured 207.0 -> 203.2 us per sub-step at 1 M atoms, never slower below
-    const int block = block_env ? block_env : 64;
-    if (gs && block != 64) fail("ghost slots: the hand-off at the end of the sub-step kernel is written for one-wave workgroups (SF_BLOCK)");
-    dim3 grid((unsigned)((lanes + block - 1) / block));
-    // The XCDs do not finish together when each gets the same number of workgroups: the two that hold the ends of the
-    // sorted range gather across the periodic face from lines no neighbour of theirs has pulled into their L2, and run
-    // ~5 % longer (workgroup timeline, profiles/r04_*).  xcd_weight_[x]: relative share of XCD x.
-    const bool xcd_can = part == 0 && S.xcd_remap == 1 && grid.x >= 2048 && mode == 0;
-    if (xcd_can && xcd_auto_ && xcd_countdown_ > 0 && --xcd_countdown_ == 0 && !xcd_sample_pending_) {
-      SF_HIP(hipMemcpyAsync(d_xcd_time_, d_xcd_time_ + 512, sizeof(int) * 512, hipMemcpyDeviceToDevice, stream_));
-      S.xcd_time = 1;
-    }
-    if (part == 0 && S.xcd_remap == 1 && xcd_weighted_ && grid.x >= 64) {
-      const int nb = (int)grid.x;
-      double wsum = 0.0;
-      for (int x = 0; x < 8; x++) wsum += xcd_weight_[x];
-      int first = 0, most = 0;
-      double acc = 0.0;
-      for (int x = 0; x < 8; x++) {
-        acc += xcd_weight_[x];
-        const int end = x == 7 ? nb : std::min(nb, (int)std::llround(nb * acc / wsum));
-        S.xcd_first[x] = first;
-        S.xcd_count[x] = std::max(0, end - first);
-        most = std::max(most, S.xcd_count[x]);
-        first = std::max(first, end);
-      }
-      S.xcd_remap = 2;
-      grid = dim3((unsigned)(8 * most));
-    }
-    stamp_last_grid_ = grid.x;
-    if (rigid_) launch_substep_rigid(gran_.style, cohe, lub, grid, block, stream_, P, S);
-    else switch (gran_.style) {
-      case 2: launch_substep_style<2>(cohe, lub, lpa, touch_prefetch_, nt_policy_, grid, block, stream_, P, S); break;
-      case 3:
-      case 1: launch_substep_style<1>(cohe, lub, lpa, touch_prefetch_, nt_policy_, grid, block, stream_, P, S); break;
-      default: launch_substep_style<0>(cohe, lub, lpa, touch_prefetch_, nt_policy_, grid, block, stream_, P, S); break;
-    }
+  if (prof_step_.size() < prof_ev_.size() / 2) prof_step_.resize(prof_ev_.size() / 2);
+  prof_step_[prof_used_ / 2] = kstep;
+  const hipEvent_t e0 = prof_ev_[prof_used_++], e1 = prof_ev_[prof_used_++];
+  SF_HIP(hipEventRecord(e0, stream_));
+  prof_open_ = (part == 2);
+  return part == 2 ? nullptr : e1;
+}
+
+// the plain kernel's grid, workgroup size and lanes per atom; grid.x == 0: this part has no atoms
+dim3 DemEngine::substep_grid(int mode, int part, StepParams& S, int& block, int& lpa)
+{
+  // enough workgroups to cover the 256 CUs even for small beds (one atom per lane either way)
+  const int nwork = part == 2 ? nb_ : (part == 1 ? n_hi_ - n_lo_ : nlocal_);
+  if (nwork <= 0) return dim3(0);
+  // lanes per atom: small systems are latency bound (one lane walks all ~12 neighbours).  Measured: 10 k atoms
+  // 17.3 -> 10.5 us per sub-step with 4 lanes, while at 100 k (1.5 waves per SIMD already) more lanes are slower
+  lpa = rigid_ ? 1 : lanes_per_atom(nwork);   // (the RIGID instantiations: one lane per atom)
+  const long long lanes = (long long)nwork * lpa;
+  // one wave per workgroup: the dispatcher then balances single waves (a 256-thread workgroup holds its CU slots
+  // until its slowest wave is done); measured 207.0 -> 203.2 us per sub-step at 1 M atoms, never slower below
+  block = block_env() ? block_env() : 64;   // (ghost slots: substep_ghost_slot_args has refused anything but 64)
+  dim3 grid((unsigned)((lanes + block - 1) / block));
+  // The XCDs do not finish together when each gets the same number of workgroups: the two that hold the ends of the
+  // sorted range gather across the periodic face from lines no neighbour of theirs has pulled into their L2, and run
+  // ~5 % longer (workgroup timeline, profiles/r04_*).  xcd_weight_[x]: relative share of XCD x.
+  const bool xcd_can = part == 0 && S.xcd_remap == 1 && grid.x >= 2048 && mode == 0;
+  if (xcd_can && xcd_auto_ && xcd_countdown_ > 0 && --xcd_countdown_ == 0 && !xcd_sample_pending_) {
+    SF_HIP(hipMemcpyAsync(d_xcd_time_, d_xcd_time_ + 512, sizeof(int) * 512, hipMemcpyDeviceToDevice, stream_));
+    S.xcd_time = 1;
   }
-  SF_HIP(hipGetLastError());
-  if (e1) SF_HIP(hipEventRecord(e1, stream_));
-  if (S.xcd_time) {   // read with the next synchronisation of the stepping loop (read_flags)
-    SF_HIP(hipMemcpyAsync(h_xcd_time_, d_xcd_time_, sizeof(int) * 512, hipMemcpyDeviceToHost, stream_));
-    xcd_sample_pending_ = true;
+  if (part == 0 && S.xcd_remap == 1 && xcd_weighted_ && grid.x >= 64) {
+    const int nb = (int)grid.x;
+    double wsum = 0.0;
+    for (int x = 0; x < 8; x++) wsum += xcd_weight_[x];
+    int first = 0, most = 0;
+    double acc = 0.0;
+    for (int x = 0; x < 8; x++) {
+      acc += xcd_weight_[x];
+      const int end = x == 7 ? nb : std::min(nb, (int)std::llround(nb * acc / wsum));
+      S.xcd_first[x] = first;
+      S.xcd_count[x] = std::max(0, end - first);
+      most = std::max(most, S.xcd_count[x]);
+      first = std::max(first, end);
+    }
+    S.xcd_remap = 2;
+    grid = dim3((unsigned)(8 * most));
   }
+  stamp_last_grid_ = grid.x;
+  return grid;
+}
+
+// the LDS-staged kernel (LDS = staged x (32 B) + v (32 B) + omega (24 B) per atom of the extended tile) or the plain one
+void DemEngine::substep_dispatch(dim3 grid, int block, int lpa, const DemPtrs& P, const StepParams& S)
+{
+  if (rigid_) return launch_substep_rigid(gran_.style, cohe_.enabled, lub_.enabled, grid, block, stream_, P, S);
+  pair_dispatch(gran_.style, cohe_.enabled, lub_.enabled, [&](auto style, auto cohe, auto lub) {
+    if (lds_active_) launch_lds_one<style, cohe, lub>(grid, (size_t)stage_cap_ * 88, stream_, P, S);
+    else flag_dispatch(S.gs_on != 0, [&](auto gs) {
+      launch_plain<style, cohe, lub, gs>(lpa, touch_prefetch_, nt_policy_, grid, block, stream_, P, S);
+    });
+  });
+}
+
+// variant builds with -DSF_EXP_STAMP=1 (sf_dem_variants.h); nothing in the shipped library
+void DemEngine::substep_stamp_record([[maybe_unused]] int mode, [[maybe_unused]] int part)
+{
 #if SF_EXP_STAMP
   // SF_STAMP_FILE=<path> [SF_STAMP_AT=<n>]: the n-th full-size launch (default 60) is recorded workgroup by workgroup
-  static const char* stamp_file = getenv("SF_STAMP_FILE");
-  static const int stamp_at = getenv("SF_STAMP_AT") ? atoi(getenv("SF_STAMP_AT")) : 60;
+  static const char* stamp_file = env_str("SF_STAMP_FILE");
+  static const int stamp_at = env_int("SF_STAMP_AT", 60);
   static int stamp_seen = 0;
   static unsigned long long* stamp_buf = nullptr;
   static size_t stamp_blocks = 0, stamp_grid = 0;
@@ -1187,6 +1153,44 @@ void DemEngine::launch_substep(int in_buf, int mode, int kstep, int part)
     }
   }
 #endif
+}
+
+void DemEngine::launch_substep(int in_buf, int mode, int kstep, int part)
+{
+  // ghost slots: every stepping launch of a decomposed engine reads the ghosts of other GPUs from the area of its number's
+  // parity and (mode 0) writes its border records into the neighbours' area of the next parity; the setup evaluation
+  // (mode 2) runs on the ghosts the border exchange has just put into the record arrays
+  const bool gs = gs_ready_ && brick_ && part == 0 && !lds_active_ && mode != 2;
+  if (!nlocal_) return substep_empty_rank(mode, kstep, gs);
+  if (part == 2 && !nb_) return;   // (no event pair opened: the interior part then times itself)
+  if (rigid_ && (part || have_subdomain_ || lds_active_ || mode == 0))
+    fail("fix rigid/nve needs the whole system on one GPU (one rank, no decomposed domain, no LDS-staged kernel)");
+  DemPtrs P = ptrs(in_buf);
+  StepParams S = step_params(mode, kstep);
+  // thermo output: the pair virial of this force evaluation, from the inputs it reads (an overlapped sub-step: before its
+  // boundary part, which the driver queues behind the ghosts of the previous exchange; before the interior part only
+  // when there is no boundary part)
+  // (never with fix rigid/nve, whose every launch is mode 1: the thermo keywords that need the virial are refused with it)
+  if (thermo_virial_on_ && mode != 0 && !rigid_ && (part != 1 || !nb_)) launch_thermo_virial(P, S);
+  if (gs) substep_ghost_slot_args(P, S);
+  if (part) substep_split_args(S, kstep, part);
+  substep_forward_pack_args(S, mode, part);
+  const hipEvent_t prof_end = substep_profile_open(kstep, part);
+  if (lds_active_ && part) fail("the LDS-staged kernel has no boundary/interior split (SF_LDS with the overlapped halo)");
+  if (lds_active_) substep_dispatch(dim3(ntiles_), 0, 0, P, S);   // (one workgroup per tile)
+  else {
+    int block = 0, lpa = 0;
+    const dim3 grid = substep_grid(mode, part, S, block, lpa);
+    if (!grid.x) return;   // (no atoms in this part; an event pair this launch opened stays as it is)
+    substep_dispatch(grid, block, lpa, P, S);
+  }
+  SF_HIP(hipGetLastError());
+  if (prof_end) SF_HIP(hipEventRecord(prof_end, stream_));
+  if (S.xcd_time) {   // read with the next synchronisation of the stepping loop (read_flags)
+    SF_HIP(hipMemcpyAsync(h_xcd_time_, d_xcd_time_, sizeof(int) * 512, hipMemcpyDeviceToHost, stream_));
+    xcd_sample_pending_ = true;
+  }
+  substep_stamp_record(mode, part);
 }
 
 void DemEngine::set_profiling(bool on)
@@ -1299,7 +1303,7 @@ static constexpr size_t kBuildLdsMax = 160 * 1024;
 
 bool DemEngine::build_parks_in_lds() const
 {
-  static const bool env = !(getenv("SF_BUILD_LDS") && !atoi(getenv("SF_BUILD_LDS")));
+  static const bool env = env_flag("SF_BUILD_LDS", true);
   return env && (size_t)M_ * kBuildLdsPerSlot <= kBuildLdsMax / 2;
 }
 
@@ -1312,7 +1316,7 @@ void DemEngine::compute_partner_tags()
   // the order they index, the current history buffer) and writes the new words into the other word array -- no staging
   // pass (98 of a 1 M-grain loose bed's 774 us per rebuild, 15 of a 100 k bed's 210).  The staged rows remain what
   // migration packs (decomposed domains) and what the tiled / LDS-staged builds read.
-  static const bool in_place_env = !(getenv("SF_HIST_IN_PLACE") && !atoi(getenv("SF_HIST_IN_PLACE")));
+  static const bool in_place_env = env_flag("SF_HIST_IN_PLACE", true);
   hist_in_place_ = in_place_env && build_parks_in_lds() && !have_subdomain_ && roots_ && grid_.tile <= 1 && !opt_lds_ &&
                    have_list_ && nlocal_ > 0 && max_neigh_used_ > 0;
   if (hist_in_place_) {
@@ -1463,8 +1467,7 @@ void DemEngine::rebuild_sort()
     hist_clean_ = true;
     // (rank and permutation in one launch: a launch less in a chain that small beds find bound by its launches -- 100 k loose
     // bed +0.9 to +2.4 % whole run; the scattered stores cost the 1 M bed nothing, +0.1 to +1 %: profiles/r06_rank_permute_ab.txt)
-    const char* rp_env = getenv("SF_RANK_PERMUTE");
-    const bool fused_rank = rp_env ? atoi(rp_env) != 0 : true;
+    const bool fused_rank = env_flag("SF_RANK_PERMUTE", true);
     if (fused_rank) {
       const RankJob rj{keys_.as<unsigned>(), first, perm_.as<int>()};
       permute_locals(perm_alt_.as<int>(), nlocal_, /*rows=*/false, &rj);
@@ -1532,7 +1535,7 @@ void DemEngine::make_periodic_ghosts()
     }
     // (the count can stay on the device until the flags are read behind the list build: bin_and_build; nghost_ < 0 =
     // "on the device".  SF_GHOST_DEFER=0: read it here, as before round 5)
-    static const bool defer = !(getenv("SF_GHOST_DEFER") && !atoi(getenv("SF_GHOST_DEFER")));
+    static const bool defer = env_flag("SF_GHOST_DEFER", true);
     if (defer && attempt == 0 && row_tables_ && !ghost_sync_) {
       nghost_ = -1;
       return;
@@ -1605,8 +1608,7 @@ void DemEngine::bin_and_build()
     const double frac = (double)h_flags_[F_PART_COAL] / (double)h_flags_[F_PART_SLOTS];
     if (hist_single_ && frac < 0.45) hist_single_ = false;
     else if (!hist_single_ && frac > 0.60) hist_single_ = true;
-    static const bool dbg = getenv("SF_DEBUG_HIST") != nullptr;
-    if (dbg) fprintf(stderr, "[sedifoam_amd] partner-side coalescing %.3f -> %s history copy\n", frac, hist_single_ ? "one" : "two");
+    if (debug_hist()) fprintf(stderr, "[sedifoam_amd] partner-side coalescing %.3f -> %s history copy\n", frac, hist_single_ ? "one" : "two");
   }
   // slot order of this list: touching neighbours first when the previous list touched fewer than about half of what
   // it listed (k_build_neigh, touch_first; hysteresis 0.40 / 0.50; SF_TOUCH_FIRST=0 / 1 pins it)
@@ -1616,8 +1618,7 @@ void DemEngine::bin_and_build()
     const bool before = touch_first_;
     if (!touch_first_ && frac < 0.40) touch_first_ = true;
     else if (touch_first_ && frac > 0.50) touch_first_ = false;
-    static const bool dbg = getenv("SF_DEBUG_HIST") != nullptr;
-    if (dbg && before != touch_first_)
+    if (debug_hist() && before != touch_first_)
       fprintf(stderr, "[sedifoam_amd] %.3f of the listed neighbours touch -> touching neighbours %s\n", frac,
               touch_first_ ? "first in their rows" : "in candidate order");
   }
@@ -1724,42 +1725,30 @@ void DemEngine::bin_and_build()
     }
     if (roots_ && cap_ > (size_t)kIdxMask) fail("more than %d atom slots per GPU: not addressable by the neighbour word", kIdxMask);
     // four lanes per atom on four consecutive records (k_build_neigh_quad): single domain without a ghost pass
-    const char* quad_env = getenv("SF_BUILD_QUAD");   // (read per build: the tests switch it inside a process)
     // (rows of full-cutoff cells -- loose beds, ~8 records -- keep four lanes busy: 405 -> 297 us on the loose 1 M bed, 60 -> 39 us
     // at 100 k grains)
     // (the 25 rows of 2-3 records of a packed bed's half-cutoff cells: two lanes, 399 -> 347-355 us at 1 M; four lanes 446)
-    const int lq = quad_env ? atoi(quad_env) : (grid_.stencil == 1 ? 4 : 2);
+    const int lq = env_int("SF_BUILD_QUAD", grid_.stencil == 1 ? 4 : 2);   // (read per build: the tests switch it inside a process)
     const bool quad = lc && !B.lb_ghost && !grid_.xslow && (lq == 2 || lq == 4 || lq == 8);
-    if (quad && lq == 2)
-      k_build_neigh_quad<2><<<div_up(nlocal_, 64), 128, lds_bytes / 2, stream_>>>(
+    auto build_quad = [&](auto lanes) {   // (128 / LQ atoms per workgroup of 128 lanes)
+      constexpr int LQ = decltype(lanes)::value;
+      k_build_neigh_quad<LQ><<<div_up(nlocal_, 128 / LQ), 128, lds_bytes / LQ, stream_>>>(
           B, xr_[cur_].as<double4>(), tag_.as<int>(), old_rows() ? numneigh_.as<int>() : nullptr, ptag_.as<int>(),
           shear_[hist_buf_].as<double>(), new_words, numneigh_old_.as<int>(), shear_[hist_buf_ ^ 1].as<double>(), d_flags_,
           xhold_.as<double>());
-    else if (quad && lq == 8)
-      k_build_neigh_quad<8><<<div_up(nlocal_, 16), 128, lds_bytes / 8, stream_>>>(
-          B, xr_[cur_].as<double4>(), tag_.as<int>(), old_rows() ? numneigh_.as<int>() : nullptr, ptag_.as<int>(),
-          shear_[hist_buf_].as<double>(), new_words, numneigh_old_.as<int>(), shear_[hist_buf_ ^ 1].as<double>(), d_flags_,
-          xhold_.as<double>());
-    else if (quad)
-      k_build_neigh_quad<4><<<div_up(nlocal_, 32), 128, lds_bytes / 4, stream_>>>(
-          B, xr_[cur_].as<double4>(), tag_.as<int>(), old_rows() ? numneigh_.as<int>() : nullptr, ptag_.as<int>(),
-          shear_[hist_buf_].as<double>(), new_words, numneigh_old_.as<int>(), shear_[hist_buf_ ^ 1].as<double>(), d_flags_,
-          xhold_.as<double>());
-    else if (lc)
-      k_build_neigh<true><<<div_up(nlocal_, 128), 128, lds_bytes, stream_>>>(
+    };
+    auto build = [&](auto kernel, int* old_words) {   // (lds_bytes: 0 without parking rows in LDS)
+      kernel<<<div_up(nlocal_, 128), 128, lds_bytes, stream_>>>(
           B, xr_[cur_].as<double4>(), tag_.as<int>(), cellLS, cellLE, cellGS, cellGE, perm_alt_.as<int>(),
           old_rows() ? numneigh_.as<int>() : nullptr, ptag_.as<int>(), shear_[hist_buf_].as<double>(), new_words,
-          numneigh_old_.as<int>(), shear_[hist_buf_ ^ 1].as<double>(), d_flags_, nullptr, xhold_.as<double>());
-    else if (!row_tables_)
-      k_build_neigh<false, false><<<div_up(nlocal_, 128), 128, 0, stream_>>>(
-          B, xr_[cur_].as<double4>(), tag_.as<int>(), cellLS, cellLE, cellGS, cellGE, perm_alt_.as<int>(),
-          old_rows() ? numneigh_.as<int>() : nullptr, ptag_.as<int>(), shear_[hist_buf_].as<double>(), new_words,
-          numneigh_old_.as<int>(), shear_[hist_buf_ ^ 1].as<double>(), d_flags_, neigh_old_.as<int>(), xhold_.as<double>());
-    else
-      k_build_neigh<false><<<div_up(nlocal_, 128), 128, 0, stream_>>>(
-          B, xr_[cur_].as<double4>(), tag_.as<int>(), cellLS, cellLE, cellGS, cellGE, perm_alt_.as<int>(),
-          old_rows() ? numneigh_.as<int>() : nullptr, ptag_.as<int>(), shear_[hist_buf_].as<double>(), new_words,
-          numneigh_old_.as<int>(), shear_[hist_buf_ ^ 1].as<double>(), d_flags_, neigh_old_.as<int>(), xhold_.as<double>());
+          numneigh_old_.as<int>(), shear_[hist_buf_ ^ 1].as<double>(), d_flags_, old_words, xhold_.as<double>());
+    };
+    if (quad && lq == 2) build_quad(int_c<2>{});
+    else if (quad && lq == 8) build_quad(int_c<8>{});
+    else if (quad) build_quad(int_c<4>{});
+    else if (lc) build(k_build_neigh<true>, nullptr);
+    else if (!row_tables_) build(k_build_neigh<false, false>, neigh_old_.as<int>());
+    else build(k_build_neigh<false>, neigh_old_.as<int>());
     // the host looks at the counts (overflow, widest row) while the partner-slot pass below is already running: it
     // needs nothing but the list, and a list that overflowed -- rare -- is built again and the pass repeated
     flags_copy_begin();
@@ -1809,7 +1798,7 @@ void DemEngine::bin_and_build()
   if (nbuilds_ < 4 || (nbuilds_ & 3) == 0 || list_stats_near_a_threshold()) measure_list();
   max_neigh_used_ = h_flags_[F_MAXNEIGH];
   // (SF_PARK_MARGIN: the tests make the rows too few on purpose -- the F_PARK_OVER path builds the list again)
-  static const int park_margin = getenv("SF_PARK_MARGIN") ? atoi(getenv("SF_PARK_MARGIN")) : 8;
+  static const int park_margin = env_int("SF_PARK_MARGIN", 8);
   park_rows_ = std::max(1, std::min(M_, max_neigh_used_ + park_margin));
   have_list_ = true;   // (xhold, the positions the skin/2 check refers to, was stored by k_build_neigh)
   hist_rows_ = false;  // (the rows read_restart left were re-injected into this list)
@@ -1839,7 +1828,7 @@ bool DemEngine::list_stats_near_a_threshold() const
 void DemEngine::measure_list()
 {
   if (!nlocal_ || !roots_) return;
-  static const bool dbg_lines = getenv("SF_DEBUG_LINES") != nullptr;
+  static const bool dbg_lines = env_set("SF_DEBUG_LINES");
   if (dbg_lines) {
     unsigned long long* d = nullptr;
     unsigned long long h[6] = {0, 0, 0, 0, 0, 0};
@@ -1870,7 +1859,6 @@ void DemEngine::measure_list()
 
 void DemEngine::choose_kernel()
 {
-  static const bool dbg = getenv("SF_DEBUG_HIST") != nullptr;
   // Non-temporal policy of the row streams (sf_dem_kernels.h, NTP): what one sub-step touches against the 256 MB
   // memory-side cache.  Records in + out 192 B, history in + out 48 B per stored copy, list words, fix arrays.
   {
@@ -1884,7 +1872,7 @@ void DemEngine::choose_kernel()
     else if (touched < mall) nt_policy_ = 0;
     else if (touched < 1.4 * mall) nt_policy_ = 3;
     else nt_policy_ = hist_single_ ? 1 : 2;
-    if (dbg && before != nt_policy_)
+    if (debug_hist() && before != nt_policy_)
       fprintf(stderr, "[sedifoam_amd] a sub-step touches %.0f MB -> non-temporal policy %d\n", touched / 1048576.0,
               nt_policy_);
   }
@@ -1908,7 +1896,7 @@ void DemEngine::choose_kernel()
   const bool before = touch_prefetch_;
   if (touch_prefetch_ && frac > 0.85) touch_prefetch_ = false;
   else if (!touch_prefetch_ && frac < 0.70) touch_prefetch_ = true;
-  if (dbg && before != touch_prefetch_)
+  if (debug_hist() && before != touch_prefetch_)
     fprintf(stderr, "[sedifoam_amd] %.3f of the listed neighbours touch -> v, omega %s\n", frac,
             touch_prefetch_ ? "prefetched by touch bit" : "always prefetched");
 }
@@ -2098,7 +2086,7 @@ void DemEngine::mark_boundary()
   n_lo_ = h_flags_[F_SEND_COUNT];
   n_hi_ = h_flags_[F_SEND_COUNT2];
   nb_ = n_lo_ + (nlocal_ - n_hi_);
-  static const bool check = getenv("SF_CHECK_BOUNDARY") && atoi(getenv("SF_CHECK_BOUNDARY"));
+  static const bool check = env_flag("SF_CHECK_BOUNDARY", false);
   if (check) {
     // list-derived classification (sent, or has a neighbour rooted on another GPU) must be inside the two ranges
     k_mark_boundary<<<div_up(nlocal_, 256), 256, 0, stream_>>>(neigh_.as<int>(), numneigh_.as<int>(),
@@ -2193,7 +2181,7 @@ void DemEngine::run(int nsteps)
     const int base = cur_;
     prof_used_ = 0;
     // queue up to where the next rebuild is expected (RebuildPredictor), not blindly to the end of the run
-    predict_.overshoot = nlocal_ >= 200000 && !(getenv("SF_QUEUE_OVERSHOOT") && !atoi(getenv("SF_QUEUE_OVERSHOOT")));
+    predict_.overshoot = nlocal_ >= 200000 && env_flag("SF_QUEUE_OVERSHOOT", true);
     const int end = k + predict_.chunk(run_base_step_ + k, nsteps - k);
     for (int s = k; s < end; s++) {
       const int in_buf = (base + (s - k)) & 1;

@@ -16,9 +16,14 @@
 
 #include "sf_dem.h"
 #include "sf_dem_gs.h"
+#include "sf_env.h"
 #include "sf_rigid.h"
 
 namespace sf {
+
+// SF_HALO_FUSED_PACK=0 as the two set_forward_tx functions see it: read at the first use, once per process
+// (brick_fused_pack_possible reads the variable itself, on every call)
+static bool fused_pack_off() { static const bool off = !env_flag("SF_HALO_FUSED_PACK", true); return off; }
 
 constexpr int kBorderDoubles = 14;   // x r | v m | omega | tag type mask
 constexpr int kMigrateFixed = 26;  // + 3*nwalls + 4*mrec + nextra
@@ -462,9 +467,8 @@ __global__ __launch_bounds__(256) void k_fill_sendslot(const int* list0, int n0,
 void DemEngine::set_forward_tx(double* tx0, double shift0, double* tx1, double shift1, double* sendbuf,
                                const int* hdr_off, int nhdr)
 {
-  static const bool off = getenv("SF_HALO_FUSED_PACK") && !atoi(getenv("SF_HALO_FUSED_PACK"));
   tx_ready_ = tx_written_ = false;
-  if (off || !nlocal_) return;
+  if (fused_pack_off() || !nlocal_) return;
   if (sendslot_.cap < cap_) sendslot_.alloc(sizeof(int), 2, cap_, stream_);
   SF_HIP(hipMemsetAsync(sendslot_.ptr, 0xFF, sizeof(int) * 2 * sendslot_.cap, stream_));
   const int tot = (int)(nsend_[0] + nsend_[1]);
@@ -773,7 +777,6 @@ __global__ __launch_bounds__(256) void k_brick_forward_unpack(DemEngine::BrickBl
 void DemEngine::brick_set_forward_tx(const BrickBlocks& snd, double* sendbuf, const int* hdr_off, int nhdr,
                                      double* const* direct_blk)
 {
-  static const bool off = getenv("SF_HALO_FUSED_PACK") && !atoi(getenv("SF_HALO_FUSED_PACK"));
   tx_ready_ = tx_written_ = false;
   // where the blocks of an exchange start: the local send buffer, or the neighbours' receive areas (two of them)
   tx_direct_ = direct_blk != nullptr;
@@ -795,7 +798,7 @@ void DemEngine::brick_set_forward_tx(const BrickBlocks& snd, double* sendbuf, co
   for (int q = 0; q < snd.n; q++)
     if ((long long)(snd.first[q + 1] - snd.first[q]) > (long long)kBlkMask)
       fail("brick_set_forward_tx: a send block of %d atoms does not fit the record slot encoding", snd.first[q + 1] - snd.first[q]);
-  if (off || !nlocal_) return;
+  if (fused_pack_off() || !nlocal_) return;
   // A brick thinner than twice the ghost cutoff in an external dimension has atoms that are ghosts of BOTH neighbours
   // along it: three choices in that dimension instead of two, up to 3 * 2 * 2 - 1 = 11 (17, 26) send directions per
   // atom -- more than the kBrickSlots = 7 records the sub-step kernel writes itself.  Such a rank keeps the stand-alone
@@ -1030,7 +1033,7 @@ void DemEngine::gs_configure(const GsSync& sync, long long first_seq)
 
 bool DemEngine::brick_fused_pack_possible() const
 {
-  if (getenv("SF_HALO_FUSED_PACK") && !atoi(getenv("SF_HALO_FUSED_PACK"))) return false;
+  if (!env_flag("SF_HALO_FUSED_PACK", true)) return false;   // (read on every call)
   // (the LDS-staged tile kernel neither writes border records nor runs the hand-off: the ranks decide this BEFORE they
   // agree on a transport -- gs_rebuild / direct_rebuild all-reduce it --, whatever build_stage_tables later finds per rank)
   if (opt_lds_) return false;

@@ -20,6 +20,7 @@
 
 #include "../../include/sedifoam_amd.h"
 #include "sf_dump.h"
+#include "sf_env.h"
 #include "sf_handles.h"
 #include "sf_roctx.h"
 
@@ -41,13 +42,15 @@ struct RcclApi {
   char path[256] = {0};   // the library these symbols come from (dladdr of ncclSend)
 };
 
+static bool debug_halo() { return env_set("SF_DEBUG_HALO"); }   // (read on every use)
+
 static RcclApi& rccl()
 {
   static RcclApi api;
   if (api.lib) return api;
   // SF_RCCL_LIB: another build of the library -- or the tests' stand-in that moves the messages of several ranks
   // sharing ONE GPU through host memory (tests/c_abi/standin_rccl.cpp; RCCL itself refuses two ranks on one device)
-  if (const char* over = getenv("SF_RCCL_LIB")) {
+  if (const char* over = env_str("SF_RCCL_LIB")) {
     api.lib = dlopen(over, RTLD_NOW | RTLD_LOCAL);
     if (!api.lib) fail("SF_RCCL_LIB=%s: %s", over, dlerror());
   }
@@ -261,7 +264,7 @@ struct HaloComm {
   }
   static void link_delay(hipStream_t st)
   {
-    static const int fake_us = getenv("SF_HALO_FAKE_DELAY_US") ? atoi(getenv("SF_HALO_FAKE_DELAY_US")) : 0;
+    static const int fake_us = env_int("SF_HALO_FAKE_DELAY_US", 0);
     if (fake_us > 0) k_fake_link_delay<<<1, 64, 0, st>>>((long long)fake_us * 100);   // wall_clock64: 100 MHz
   }
 };
@@ -431,7 +434,7 @@ static void slab_rebuild(SfLammps& S, HaloComm& hc)
   const auto t_begin = std::chrono::steady_clock::now();
   DemEngine& e = S.eng;
   hipStream_t st = e.stream();
-  static const bool dbgt = getenv("SF_DEBUG_REBUILD_PHASES") != nullptr;
+  static const bool dbgt = env_set("SF_DEBUG_REBUILD_PHASES");
   auto tprev = t_begin;
   auto lap = [&](const char* what) {
     if (!dbgt) return;
@@ -730,7 +733,7 @@ static DemEngine::DirectSync direct_sync(const HaloComm& hc, int seq, int par)
   s.par = par;
   s.my_sync = D.my_sync;
   for (int p = 0; p < 32; p++) s.peer_sync[p] = p < hc.world ? D.peer_sync[p] : nullptr;
-  static const double secs = getenv("SF_HALO_DIRECT_TIMEOUT") ? atof(getenv("SF_HALO_DIRECT_TIMEOUT")) : 20.0;
+  static const double secs = env_double("SF_HALO_DIRECT_TIMEOUT", 20.0);
   s.max_ticks = (long long)(secs * 1.0e8);   // wall_clock64: 100 MHz
   return s;
 }
@@ -758,7 +761,7 @@ static void direct_messages(HaloComm& hc, hipStream_t st, const std::vector<int>
 // anything; a library default of "auto" would put an unproven transport under every host.)
 static void direct_init(SfLammps& S, HaloComm& hc)
 {
-  const char* env = getenv("SF_HALO_DIRECT");
+  const char* env = env_str("SF_HALO_DIRECT");
   // ("2" / "slots": ghost slots, must come up; "auto2": ghost slots, or the RCCL exchange when the bring-up fails)
   const bool slots = env && (!strcmp(env, "2") || !strcmp(env, "slots") || !strcmp(env, "auto2"));
   const int want = !env ? 0 : (!strcmp(env, "auto") || !strcmp(env, "auto2") ? -1 : (slots ? 1 : atoi(env)));
@@ -833,7 +836,7 @@ static void direct_init(SfLammps& S, HaloComm& hc)
       const long long a = D.h_msg[(size_t)(W + p) * K + 10], b = D.h_msg[(size_t)(W + q) * K + 10];
       if (a > 0 && a == b) shared_device = true;
     }
-  if (slots && shared_device && !self_only && !(getenv("SF_HALO_SHARED_DEVICE_OK") && atoi(getenv("SF_HALO_SHARED_DEVICE_OK")))) {
+  if (slots && shared_device && !self_only && !env_flag("SF_HALO_SHARED_DEVICE_OK", false)) {
     if (strcmp(env, "auto2") != 0) {
       delete hc.direct;
       hc.direct = nullptr;
@@ -841,7 +844,7 @@ static void direct_init(SfLammps& S, HaloComm& hc)
            "(use auto2, auto or 1; SF_HALO_SHARED_DEVICE_OK=1 overrides for small test beds)", env);
     }
     slots_effective = false;   // auto2: the receive areas (SF_HALO_DIRECT=auto), which ranks sharing a device can run
-    if (getenv("SF_DEBUG_HALO")) fprintf(stderr, "[sedifoam_amd] rank %d: ranks share a GPU, ghost slots -> receive areas\n", hc.rank);
+    if (debug_halo()) fprintf(stderr, "[sedifoam_amd] rank %d: ranks share a GPU, ghost slots -> receive areas\n", hc.rank);
   }
   if (ok != 0.0) {
     // the first round: vote + flag to every rank, every rank's flag awaited (no records yet)
@@ -849,7 +852,7 @@ static void direct_init(SfLammps& S, HaloComm& hc)
     DemEngine::DirectSync s = direct_sync(hc, 1, 0);
     // (the wait of SF_HALO_DIRECT_TIMEOUT -- direct_sync -- capped at 5 s unless the variable asks for more: ranks that share
     // one GPU time-slice it and need longer)
-    if (!getenv("SF_HALO_DIRECT_TIMEOUT") && s.max_ticks > 500000000LL) s.max_ticks = 500000000LL;
+    if (!env_set("SF_HALO_DIRECT_TIMEOUT") && s.max_ticks > 500000000LL) s.max_ticks = 500000000LL;
     ok = e.brick_direct_probe(none, s) ? 1.0 : 0.0;
     if (ok == 0.0) why = "the first flag round timed out";
     ok = slab_allreduce(hc, st, ok, ncclMin);
@@ -859,7 +862,7 @@ static void direct_init(SfLammps& S, HaloComm& hc)
     delete hc.direct;
     hc.direct = nullptr;
     if (want == 1) fail("SF_HALO_DIRECT=1: direct ghost writes did not come up on every rank (%s)", why.empty() ? "another rank" : why.c_str());
-    if (getenv("SF_DEBUG_HALO")) fprintf(stderr, "[sedifoam_amd] rank %d: direct ghost writes off, RCCL exchange (%s)\n", hc.rank, why.empty() ? "another rank failed" : why.c_str());
+    if (debug_halo()) fprintf(stderr, "[sedifoam_amd] rank %d: direct ghost writes off, RCCL exchange (%s)\n", hc.rank, why.empty() ? "another rank failed" : why.c_str());
     return;
   }
   D.on = true;
@@ -880,7 +883,7 @@ static void direct_init(SfLammps& S, HaloComm& hc)
     (void)slab_allreduce(hc, st, 1.0, ncclMin);
     e.gs_configure(y, 2);
   }
-  if (getenv("SF_DEBUG_HALO"))
+  if (debug_halo())
     fprintf(stderr, "[sedifoam_amd] rank %d: direct ghost writes on (%d ranks, %s)\n", hc.rank, W,
             D.mode == 2 ? "ghost slots" : "receive areas");
 }
@@ -898,7 +901,7 @@ static bool direct_lost(SfLammps& S, HaloComm& hc, const std::string& why)
   S.eng.gs_off();
   if (D.must)
     fail("SF_HALO_DIRECT: the direct transport was lost at a rebuild (%s)", why.empty() ? "on another rank" : why.c_str());
-  if (getenv("SF_DEBUG_HALO"))
+  if (debug_halo())
     fprintf(stderr, "[sedifoam_amd] rank %d: direct ghost writes off from this rebuild on, RCCL exchange (%s)\n", hc.rank,
             why.empty() ? "another rank failed" : why.c_str());
   return false;
@@ -1273,9 +1276,9 @@ static int brick_halo_run(SfLammps& S, HaloComm& hc, int first_k, int end_k, int
     // is the stand-alone pack in front of a launch no sub-step kernel has written the records for (start of a run, first
     // launch after a rebuild) and, at the end of a piece that stops early, the wait for the last votes
     static FILE* tr = nullptr;   // (SF_DEBUG_HALO_TRACE=<prefix>: one line per piece and rank, flushed: what a stalled rank did last)
-    if (!tr && getenv("SF_DEBUG_HALO_TRACE")) {
+    if (!tr && env_set("SF_DEBUG_HALO_TRACE")) {
       char name[512];
-      snprintf(name, sizeof(name), "%s.%d", getenv("SF_DEBUG_HALO_TRACE"), hc.rank);
+      snprintf(name, sizeof(name), "%s.%d", env_str("SF_DEBUG_HALO_TRACE"), hc.rank);
       tr = fopen(name, "w");
     }
     if (tr) {
@@ -1294,7 +1297,7 @@ static int brick_halo_run(SfLammps& S, HaloComm& hc, int first_k, int end_k, int
               e.halo_timeout_peer(), e.halo_timeout_seen());
       fflush(tr);
     }
-    if (e.halo_timeout() && getenv("SF_DEBUG_HALO")) {
+    if (e.halo_timeout() && debug_halo()) {
       // what this rank sees of everybody: the (flag << 32) | vote word of every sending rank
       int lines[32 * DemEngine::kSyncStride];
       (void)hipMemcpy(lines, hc.direct->my_sync, sizeof(int) * DemEngine::kSyncStride * hc.world, hipMemcpyDeviceToHost);
@@ -1678,7 +1681,7 @@ int sf_slab_init(void* ptr, const char* id128, int rank, int world, double xlo, 
   const double sublo = xlo + rank * w, subhi = rank == world - 1 ? xhi : xlo + (rank + 1) * w;
   L->eng.set_subdomain(rank, world, sublo, subhi);
   sf::slab_scratch(*hc);
-  if (const char* q = getenv("SF_QUEUE_PREDICT")) hc->predict.on = atoi(q) != 0;
+  hc->predict.on = sf::env_flag("SF_QUEUE_PREDICT", hc->predict.on);
   SF_API_END(0)
 }
 
@@ -1702,7 +1705,7 @@ int sf_brick_init(void* ptr, const char* id128, int rank, int world, int px, int
   // SF_HALO_SELF_COMM=1 (development, one rank): the periodic dimensions are external too -- the rank exchanges border
   // records and migrating atoms with ITSELF through the same code as with a neighbour (what the exchange costs next to
   // the sub-step kernel without another process' kernels on the GPU: tests/trace_selfcomm.sh)
-  const bool self_comm = world == 1 && getenv("SF_HALO_SELF_COMM") && atoi(getenv("SF_HALO_SELF_COMM")) != 0;
+  const bool self_comm = world == 1 && sf::env_flag("SF_HALO_SELF_COMM", false);
   for (int k = 0; k < 3; k++) {
     B.ext[k] = B.P[k] > 1 || (self_comm && B.periodic[k]);
     ext[k] = B.ext[k] ? 1 : 0;
@@ -1713,7 +1716,7 @@ int sf_brick_init(void* ptr, const char* id128, int rank, int world, int px, int
   L->eng.set_subdomain3(rank, world, lo, hi, ext);
   sf::slab_scratch(*hc);
   sf::brick_topology(*hc, L->eng);
-  if (const char* q = getenv("SF_QUEUE_PREDICT")) hc->predict.on = atoi(q) != 0;
+  hc->predict.on = sf::env_flag("SF_QUEUE_PREDICT", hc->predict.on);
   sf::direct_init(*L, *hc);
   SF_API_END(0)
 }

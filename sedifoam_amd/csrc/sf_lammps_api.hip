@@ -16,6 +16,7 @@
 
 #include "../../include/sedifoam_amd.h"
 #include "sf_dump.h"
+#include "sf_env.h"
 #include "sf_handles.h"
 #include "sf_restart.h"
 #include "sf_rigid.h"
@@ -641,7 +642,7 @@ int sf_lammps_open_world(int argc, char** argv, intptr_t comm, int rank, int wor
     int local = rank;
     for (const char* name : {"SF_DEVICE", "OMPI_COMM_WORLD_LOCAL_RANK", "MPI_LOCALRANKID", "MV2_COMM_WORLD_LOCAL_RANK",
                              "SLURM_LOCALID", "LOCAL_RANK"})
-      if (const char* v = getenv(name)) {
+      if (const char* v = sf::env_str(name)) {
         local = atoi(v);
         break;
       }

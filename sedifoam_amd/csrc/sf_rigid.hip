@@ -8,6 +8,7 @@
 #include <cmath>
 #include <map>
 
+#include "sf_dem_dispatch.h"
 #include "sf_dem_kernels.h"
 
 namespace sf {
@@ -15,25 +16,12 @@ namespace sf {
 // ------------------------------------------------------------------------------------------------
 // the force evaluation: k_substep with the body-mass branch of the pair law, storing force / torque only
 // ------------------------------------------------------------------------------------------------
-template <int STYLE>
-static void launch_rigid_style(bool cohe, bool lub, dim3 grid, int block, hipStream_t s, const DemPtrs& P,
-                               const StepParams& S)
-{
-  if (cohe && lub) k_substep<STYLE, true, true, 1, false, 0, false, true><<<grid, block, 0, s>>>(P, S);
-  else if (cohe) k_substep<STYLE, true, false, 1, false, 0, false, true><<<grid, block, 0, s>>>(P, S);
-  else if (lub) k_substep<STYLE, false, true, 1, false, 0, false, true><<<grid, block, 0, s>>>(P, S);
-  else k_substep<STYLE, false, false, 1, false, 0, false, true><<<grid, block, 0, s>>>(P, S);
-}
-
 void launch_substep_rigid(int style, bool cohe, bool lub, dim3 grid, int block, hipStream_t s, const DemPtrs& P,
                           const StepParams& S)
 {
-  switch (style) {
-    case 2: launch_rigid_style<2>(cohe, lub, grid, block, s, P, S); break;
-    case 3:
-    case 1: launch_rigid_style<1>(cohe, lub, grid, block, s, P, S); break;
-    default: launch_rigid_style<0>(cohe, lub, grid, block, s, P, S); break;
-  }
+  pair_dispatch(style, cohe, lub, [&](auto st, auto c, auto l) {
+    k_substep<st, c, l, 1, false, 0, false, true><<<grid, block, 0, s>>>(P, S);
+  });
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 // sf_smooth.hip -- see sf_smooth.h (enhancedCloud::smoothField, lammpsFoam/enhancedCloud.C:790-907).
 #include "sf_smooth.h"
 #include "sf_roctx.h"
+#include "sf_env.h"
 
 #include <algorithm>
 #include <cmath>
@@ -372,7 +373,7 @@ void DiffusionSmoother::configure(const int n[3], const double dx[3], const doub
   SF_HIP(hipMalloc(&scal_, sizeof(double) * S_N));
   SF_HIP(hipHostMalloc(&h_scal_, sizeof(double) * S_N));
   // Chebyshev: spectrum bounds and the iteration count for a residual factor of 1e-15
-  use_cg_ = getenv("SF_SMOOTH_CG") && atoi(getenv("SF_SMOOTH_CG")) != 0;
+  use_cg_ = env_flag("SF_SMOOTH_CG", false);
   lmin_ = 1.0;
   lmax_ = 1.0 + 4.0 * (c_[0] + c_[1] + c_[2]);
   const double kappa = lmax_ / lmin_;
@@ -382,7 +383,7 @@ void DiffusionSmoother::configure(const int n[3], const double dx[3], const doub
   SF_HIP(hipMalloc(&cheb_, sizeof(double) * 3 * kMaxCheb * ncells_));
   // spectral path: DCT-II matrices and scaled eigenvalues of the three directions
   use_spectral_ = !use_cg_ && std::max(n_[0], std::max(n_[1], n_[2])) <= kMaxSpectral &&
-                  !(getenv("SF_SMOOTH_SPECTRAL") && atoi(getenv("SF_SMOOTH_SPECTRAL")) == 0);
+                  env_flag("SF_SMOOTH_SPECTRAL", true);
   if (graded && !use_spectral_)
     fail("diffusion smoothing on a graded block needs the dense-transform solver (at most %d cells per direction, "
          "no SF_SMOOTH_CG / SF_SMOOTH_SPECTRAL=0)", kMaxSpectral);

@@ -7,6 +7,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "sf_dem.h"
+#include "sf_env.h"
 
 namespace sf {
 
@@ -201,9 +202,9 @@ void exclusive_scan_i32(void*& tmp, size_t& tmp_bytes, const int* in, int* out, 
 {
   if (n <= 0) return;
   // (read per call -- a rebuild-time function: the tests switch them inside one process)
-  const bool own_scan = !(getenv("SF_ROCPRIM_SCAN") && atoi(getenv("SF_ROCPRIM_SCAN")));
-  const int own_min = getenv("SF_SCAN_MIN") ? atoi(getenv("SF_SCAN_MIN")) : (1 << 16);   // (tests: 1)
-  if (own_scan && n <= kOneBlockMax && in != out && !getenv("SF_SCAN_MIN") && (reinterpret_cast<uintptr_t>(in) & 15) == 0 &&
+  const bool own_scan = !env_flag("SF_ROCPRIM_SCAN", false);
+  const int own_min = env_int("SF_SCAN_MIN", 1 << 16);   // (tests: 1)
+  if (own_scan && n <= kOneBlockMax && in != out && !env_set("SF_SCAN_MIN") && (reinterpret_cast<uintptr_t>(in) & 15) == 0 &&
       (reinterpret_cast<uintptr_t>(out) & 15) == 0) {   // (SF_SCAN_MIN: the tests force the tiled scan)
     k_scan_one_block<<<1, 1024, 0, s>>>(in, n, out);
     SF_HIP(hipGetLastError());

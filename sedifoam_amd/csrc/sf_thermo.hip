@@ -26,6 +26,8 @@
 #include <vector>
 
 #include "../../include/sedifoam_amd.h"
+#include "sf_dem_dispatch.h"
+#include "sf_env.h"
 #include "sf_handles.h"
 #include "sf_thermo.h"
 
@@ -439,16 +441,10 @@ int thermo_virial_blocks(int nlocal) { return std::min(kVirialMaxBlocks, std::ma
 
 void thermo_virial_launch(const DemPtrs& P, const StepParams& S, bool lub, double* out, int nblocks, hipStream_t st)
 {
-  const int style = S.gran.style == 3 ? 1 : S.gran.style;   // (plain gran/hooke: the Hookean law branches on the style)
   const dim3 g(nblocks), b(kThermoBlock);
-  switch (style * 2 + (lub ? 1 : 0)) {
-    case 0: k_thermo_virial<0, false><<<g, b, 0, st>>>(P, S, out); break;
-    case 1: k_thermo_virial<0, true><<<g, b, 0, st>>>(P, S, out); break;
-    case 2: k_thermo_virial<1, false><<<g, b, 0, st>>>(P, S, out); break;
-    case 3: k_thermo_virial<1, true><<<g, b, 0, st>>>(P, S, out); break;
-    case 4: k_thermo_virial<2, false><<<g, b, 0, st>>>(P, S, out); break;
-    default: k_thermo_virial<2, true><<<g, b, 0, st>>>(P, S, out); break;
-  }
+  style_dispatch(S.gran.style, [&](auto style) {
+    flag_dispatch(lub, [&](auto l) { k_thermo_virial<style, l><<<g, b, 0, st>>>(P, S, out); });
+  });
   SF_HIP(hipGetLastError());
 }
 
@@ -469,9 +465,9 @@ void thermo_open_args(SfLammps& L, int argc, char** argv)
   }
   // hosts that pass argv = NULL (the reference's softParticleCloud.C): the same through the environment
   if (!have_scr)
-    if (const char* v = getenv("SF_SCREEN")) have_scr = !(scr = v).empty();
+    if (const char* v = env_str("SF_SCREEN")) have_scr = !(scr = v).empty();
   if (!have_log)
-    if (const char* v = getenv("SF_LOG")) have_log = !(lg = v).empty();
+    if (const char* v = env_str("SF_LOG")) have_log = !(lg = v).empty();
   if (!have_scr && !have_log) return;   // (the default: none and none)
   Thermo& T = ensure(L);
   if (have_scr) set_screen(L, T, scr);

@@ -387,6 +387,38 @@ def test_kernel_variants_agree_with_oracle(env, monkeypatch):
                         lub=(1.0e-3, 1, 1, 1.001e-3, 1.1e-3, 1, 1)), steps=(1, 30))
 
 
+DISPATCH_PAIRS = {"hooke": dict(pair="hooke", kn=2.0e3, gamman=50.0, dampflag=1), "hertz": {},
+                  "hooke_plain": dict(pair="hooke_plain", kn=2.0e3, gamman=50.0, dampflag=1)}
+DISPATCH_FAMILIES = {"lpa1": {"SF_LPA": "1"}, "lpa2": {"SF_LPA": "2"}, "lpa4": {"SF_LPA": "4"},
+                     "lds": {"SF_LDS": "1", "SF_TILE": "4", "SF_SUB": "1"}}
+
+
+# (left out: plain gran/hooke with neither cohesion nor lubrication.  Its torques are sums of velocity-damping forces alone, and
+# on this bed they sit at 1.23e-12 of the largest against the 1e-12 of _run_case, in all four families alike, before the
+# mapping was restated as after; test_periodic_plain_hooke_bed_with_wall_and_rebuilds runs that kernel with its own bound)
+DISPATCH_CASES = [(p, c, l, f) for p in sorted(DISPATCH_PAIRS) for c in (False, True) for l in (False, True)
+                  for f in sorted(DISPATCH_FAMILIES) if (p, c, l) != ("hooke_plain", False, False)]
+
+
+@pytest.mark.parametrize("pair,cohe,lub,family", DISPATCH_CASES,
+                         ids=["-".join((p, "cohe" if c else "nocohe", "lub" if l else "nolub", f)) for p, c, l, f in DISPATCH_CASES])
+def test_dispatch_matrix_every_pair_setting_reaches_its_own_kernel(pair, cohe, lub, family, monkeypatch):
+    """From the run-time settings to the kernel instantiation (pair_dispatch, sf_dem_dispatch.h): every pair style x fix
+    cohesive off / on x lubricate/poly off / on, through the plain kernel with 1, 2 and 4 lanes per atom and through the
+    LDS-staged kernel, each against the oracle with the same settings.  A few dozen polydisperse grains (about half of the
+    neighbours touch, the others within the reach of cohesion and lubrication), setup + 20 sub-steps: a swapped cohe / lub
+    or a wrongly folded style gives other forces."""
+    for k, v in DISPATCH_FAMILIES[family].items():
+        monkeypatch.setenv(k, v)
+    bed = _bed((4, 4, 4), periodic=True, seed=11, poly=(0.85e-3, 1.0e-3), spacing=0.95)
+    cfg = dict(BASE, skin=0.2e-3, **DISPATCH_PAIRS[pair])
+    if cohe:
+        cfg["cohesive"] = (1.0e-13, 1.0e-7, 1.0e-7, 1.0e-4, 1)
+    if lub:
+        cfg["lub"] = (1.0e-3, 1, 1, 1.001e-3, 1.1e-3, 1, 1)
+    _run_case(bed, cfg, steps=(1, 19))
+
+
 def test_list_build_with_four_lanes_per_atom_gives_the_same_bits(monkeypatch):
     """k_build_neigh_quad (four or eight lanes per atom on as many consecutive records of a row, single domain without a ghost pass)
     builds the list k_build_neigh builds, word for word: a hot loose periodic bed (ghost-free build, touching neighbours
