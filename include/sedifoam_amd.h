@@ -124,6 +124,21 @@ int sf_lammps_get_rigid(void *ptr, int max_bodies, int *natoms, double *masstota
  * {GPU ms of the last pack, host ms until its pinned copy had landed, host ms until its file was renamed, 0}, after
  * waiting for the writer */
 int sf_lammps_restart_cost(void *ptr, int timing_on, double *out4);
+/* the contact network (the script commands `compute ID group pair/local ...` and `dump ID group local ...` write the same
+ * rows as text): one row per touching pair (rsq < (radi + radj)^2) of two atoms of `group` (NULL or "": all), evaluated now
+ * from the state as it stands -- x, v, omega, the shear history sf_dem_get_history returns -- with shearupdate = false;
+ * nothing is stored and the run goes on with the same bits.  tag1 < tag2; values is row-major [max][9]: dist, force (the
+ * signed normal force r ccel, repulsive > 0), fx fy fz (its vector del ccel on tag1, del = x(tag1) - x(tag2) by minimum
+ * image), p1 p2 p3 (the tangential force on tag1), p4 (its magnitude).  Walls, fix cohesive and lubrication are not in a
+ * row.  Returns the number of rows, or -1 (sf_last_error); rows that do not fit in max are not written, the count is still
+ * returned.  Order: that of a `dump local` frame written at this moment (atom index, then partner tag).  One rank, a
+ * granular pair style without lubricate/poly, no fix rigid/nve, after the first run (run 0 will do). */
+long long sf_lammps_get_contacts(void *ptr, const char *group, long long max, int *tag1, int *tag2, double *values);
+/* kernel launches made for contact rows so far (0 for a run without compute pair/local output and without queries) */
+int sf_lammps_contact_launches(void *ptr, long long *launches);
+/* measurement (tools/contact_cost.py): out3 = {GPU ms of count + scan + rows, GPU ms of the text of every column (lines +
+ * scan + compact), rows} of one evaluation now, from HIP events; nothing is written */
+int sf_lammps_contact_cost(void *ptr, const char *group, double *out3);
 /* library.h:61-63 (particle injection / removal; tag[] is double in the reference) */
 int sf_lammps_create_particle(void *ptr, int npAdd, const double *position, const double *tag,
                               double diameter, double rho, int type, const double *vel);

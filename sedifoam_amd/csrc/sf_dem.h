@@ -619,6 +619,13 @@ class DemEngine {
   const double* thermo_virial_partials() const { return thermo_vbuf_; }
   int thermo_virial_blocks() const { return thermo_vblocks_; }   // partial rows of the last pass (0: no owned atoms)
   long long thermo_virial_launches() const { return thermo_vlaunches_; }
+  // ---- compute pair/local (sf_contacts.hip): the kernel arguments of a pair-force evaluation on the state as it stands --
+  // the records, the list and the history buffer the next sub-step launch would read (mode 2: nothing is advanced).
+  // false: no list was built yet
+  bool contact_view(DemPtrs* P, StepParams* S) const;
+  int pair_gran_style() const { return gran_.style; }
+  bool pair_lubricate_on() const { return lub_.enabled != 0; }
+  bool decomposed() const { return have_subdomain_; }
   // ---- fix rigid/nve (sf_rigid.h, sf_rigid.hip): bodies of spheres, one domain ----
   // bodystyle 0 single (the atoms of the group are one body), 1 group (one body per listed group), 2 molecule
   void rigid_define(int bodystyle, int groupbit, const std::vector<int>& groupbits);

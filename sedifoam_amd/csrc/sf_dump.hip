@@ -10,6 +10,10 @@
 //   k_dump_compact one lane per slot byte: the lines, contiguous
 // then an asynchronous copy into one of two pinned host buffers.  A writer thread waits for the copy, writes the header
 // and the bytes and flushes; the run goes on meanwhile.  A frame waits only for its buffer's previous write.
+//
+// `dump ID group local N file index c_ID[k] ...` ([3P] DumpLocal) goes the same way with another first launch: the rows of
+// the compute pair/local it names are evaluated (sf_contacts.hip: count, scan, rows) and k_contact_lines, one lane per row,
+// fills the slots.  Schedule, `*`, undump, the step-0 frame and the writer are the shared code below.
 #include <algorithm>
 #include <climits>
 #include <condition_variable>
@@ -27,6 +31,7 @@
 
 #include "../../include/sedifoam_amd.h"
 #include "sf_common.h"
+#include "sf_contacts.h"
 #include "sf_dump.h"
 #include "sf_dump_fmt.h"
 #include "sf_handles.h"
@@ -161,14 +166,17 @@ struct DevBuf {
 struct Pipeline {
   DevBuf slots, len, off, out, scan, small;
   // format nslots slots of `stride` bytes (the caller's kernel `fill` writes them and their lengths into len), then
-  // compact; returns the byte count (synchronises the stream once, after the scan) -- the bytes are in out.p
+  // compact; returns the byte count (synchronises the stream once, after the scan) -- the bytes are in out.p.
+  // ev: four events around the launches in front of and behind that wait (tools/contact_cost.py)
   template <class Fill>
-  size_t run(long long nslots, int stride, bool zero_len, hipStream_t s, Fill fill, unsigned long long* h_small)
+  size_t run(long long nslots, int stride, bool zero_len, hipStream_t s, Fill fill, unsigned long long* h_small,
+             hipEvent_t* ev = nullptr)
   {
     char* d_slots = static_cast<char*>(slots.get((size_t)nslots * stride + 1, s));
     auto* d_len = static_cast<unsigned long long*>(len.get(sizeof(unsigned long long) * (nslots + 1), s));
     auto* d_off = static_cast<unsigned long long*>(off.get(sizeof(unsigned long long) * (nslots + 1), s));
     auto* d_small = static_cast<unsigned long long*>(small.get(4 * sizeof(unsigned long long), s));
+    if (ev) SF_HIP(hipEventRecord(ev[0], s));
     SF_HIP(hipMemsetAsync(d_small, 0, 4 * sizeof(unsigned long long), s));
     if (zero_len) SF_HIP(hipMemsetAsync(d_len, 0, sizeof(unsigned long long) * (nslots + 1), s));
     else SF_HIP(hipMemsetAsync(d_len + nslots, 0, sizeof(unsigned long long), s));
@@ -180,17 +188,20 @@ struct Pipeline {
     void* tmp = scan.get(need, s);
     SF_HIP(rocprim::exclusive_scan(tmp, need, d_len, d_off, 0ull, (size_t)nslots + 1,
                                    rocprim::plus<unsigned long long>(), s));
+    if (ev) SF_HIP(hipEventRecord(ev[1], s));
     SF_HIP(hipMemcpyAsync(h_small, d_off + nslots, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     SF_HIP(hipMemcpyAsync(h_small + 1, d_small, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     SF_HIP(hipStreamSynchronize(s));
     const size_t total = (size_t)h_small[0];
     char* d_out = static_cast<char*>(out.get(total + 1, s));
+    if (ev) SF_HIP(hipEventRecord(ev[2], s));
     if (total) {
       const long long bytes = nslots * stride;
       const long long nb = std::min<long long>((bytes + 255) / 256, 1 << 20);
       k_dump_compact<<<(unsigned)nb, 256, 0, s>>>(d_slots, stride, d_len, d_off, nslots, d_out);
       SF_HIP(hipGetLastError());
     }
+    if (ev) SF_HIP(hipEventRecord(ev[3], s));
     return total;
   }
 };
@@ -208,6 +219,9 @@ struct Dump {
   Cols cols{};
   int stride = 1;
   bool sort = false, multifile = false, multiproc = false;
+  bool local = false;    // dump local: the rows of `compute` (a compute pair/local), columns lcols
+  std::string compute;
+  ContactCols lcols{};
   bool gather = false;   // one file written by rank 0 on more than one rank
   long long last = -1;   // the step of the last frame ([3P] Output::last_dump)
   FILE* fp = nullptr;    // the single file (not `*`), opened and truncated by the dump command
@@ -349,8 +363,22 @@ void write_frame(SfLammps& L, DumpSet& S, Dump& d)
   const long long nslots = d.sort ? (long long)e.max_tag() : (long long)n;
   if (!d.h_small) SF_HIP(hipHostMalloc(reinterpret_cast<void**>(&d.h_small), 4 * sizeof(unsigned long long)));
   size_t total = 0;
-  unsigned long long natoms = 0;
-  if (n > 0 && nslots > 0) {
+  unsigned long long natoms = 0;   // (dump local: the rows)
+  if (d.local) {
+    // the rows are those of the compute's group, evaluated now; the stream is synchronised for their count, and once more
+    // below for the byte count
+    int groupbit = 1;
+    compute_lookup(L, d.compute, nullptr, &groupbit);
+    const ContactRows R = contact_rows(L, groupbit);
+    natoms = (unsigned long long)R.n;
+    if (R.n > 0) {
+      const ContactCols cols = d.lcols;
+      const int stride = d.stride;
+      total = d.pipe.run(R.n, stride, false, s, [&](char* slots, unsigned long long* len, unsigned long long*) {
+        contact_lines_launch(R, cols, stride, slots, len, s);
+      }, d.h_small);
+    }
+  } else if (n > 0 && nslots > 0) {
     const int groupbit = d.groupbit, sorted = d.sort ? 1 : 0, stride = d.stride;
     const Cols cols = d.cols;
     total = d.pipe.run(nslots, stride, d.sort, s, [&](char* slots, unsigned long long* len, unsigned long long* small) {
@@ -390,10 +418,14 @@ void write_frame(SfLammps& L, DumpSet& S, Dump& d)
   double lo[3], hi[3];
   int per[3];
   e.box(lo, hi, per);
+  // ([3P] DumpLocal::write_header likewise: NUMBER OF ENTRIES / ENTRIES in place of NUMBER OF ATOMS / ATOMS; from memory of
+  // LAMMPS 1Feb14 as well, not checked against a LAMMPS source)
   std::vector<char> hb(512 + d.columns.size());
   const int hn = snprintf(hb.data(), hb.size(),
-                          "ITEM: TIMESTEP\n%lld\nITEM: NUMBER OF ATOMS\n%llu\nITEM: BOX BOUNDS %s %s %s\n%g %g\n%g %g\n"
-                          "%g %g\nITEM: ATOMS %s\n",
+                          d.local ? "ITEM: TIMESTEP\n%lld\nITEM: NUMBER OF ENTRIES\n%llu\nITEM: BOX BOUNDS %s %s %s\n%g %g\n"
+                                    "%g %g\n%g %g\nITEM: ENTRIES %s\n"
+                                  : "ITEM: TIMESTEP\n%lld\nITEM: NUMBER OF ATOMS\n%llu\nITEM: BOX BOUNDS %s %s %s\n%g %g\n"
+                                    "%g %g\n%g %g\nITEM: ATOMS %s\n",
                           step, natoms, per[0] ? "pp" : "ff", per[1] ? "pp" : "ff", per[2] ? "pp" : "ff", lo[0], hi[0],
                           lo[1], hi[1], lo[2], hi[2], d.columns.c_str());
   Job j{&d, b, total, std::string(hb.data(), hn), std::string()};
@@ -445,8 +477,10 @@ void dump_command(SfLammps& L, const std::vector<std::string>& w)
 {
   if (w.size() < 6) sf::fail("Illegal dump command");
   const std::string& style = w[3];
-  if (style != "custom") sf::fail("Invalid dump style %s (this engine writes dump custom only)", style.c_str());
-  if (w.size() < 7) sf::fail("Illegal dump custom command");
+  const bool local = style == "local";
+  if (style != "custom" && !local)
+    sf::fail("Invalid dump style %s (this engine writes dump custom and dump local)", style.c_str());
+  if (w.size() < 7) sf::fail("Illegal dump %s command", style.c_str());
   DumpSet& S = ensure_set(L);
   S.check_error();
   if (S.find(w[1])) sf::fail("Reuse of dump ID");
@@ -466,7 +500,51 @@ void dump_command(SfLammps& L, const std::vector<std::string>& w)
   d->gather = L.world_size > 1 && !d->multiproc;
   d->cols.n = 0;
   d->stride = 1;
-  for (size_t k = 6; k < w.size(); k++) {
+  d->local = local;
+  if (local) {
+    // [3P] DumpLocal::parse_fields: index | c_ID | c_ID[k].  The rows are those of ONE compute pair/local -- its group
+    // selects them; the dump's own group plays no part, a row has no single atom
+    if (d->multiproc || L.world_size > 1 || L.decomposed)
+      sf::fail("dump local: one rank and one file only (no %% in the file name, no decomposed domain)");
+    std::vector<unsigned char> values;
+    for (size_t k = 6; k < w.size(); k++) {
+      int c = -1;
+      if (w[k] == "index") c = kContactIndex;
+      else if (w[k].compare(0, 2, "c_") == 0) {
+        std::string id = w[k].substr(2);
+        long idx = 0;
+        const size_t br = id.find('[');
+        if (br != std::string::npos) {
+          char* e2 = nullptr;
+          idx = std::strtol(id.c_str() + br + 1, &e2, 10);
+          if (e2 == id.c_str() + br + 1 || *e2 != ']' || e2[1] || idx < 1)
+            sf::fail("Invalid attribute %s in dump local command", w[k].c_str());
+          id.resize(br);
+        }
+        if (d->compute.empty()) {
+          compute_lookup(L, id, &values, nullptr);   // "Could not find dump local compute ID"
+          d->compute = id;
+        } else if (id != d->compute)
+          sf::fail("dump local: every c_ column must name the same compute (%s and %s): the rows of two computes are "
+                   "not the same rows", d->compute.c_str(), id.c_str());
+        if (br == std::string::npos) {
+          if (values.size() != 1) sf::fail("Dump local compute does not compute local vector: %s", w[k].c_str());
+          idx = 1;
+        } else if (idx > (long)values.size())
+          sf::fail("Dump local compute vector is accessed out-of-range: %s", w[k].c_str());
+        c = values[idx - 1];
+      } else
+        sf::fail("Invalid attribute %s in dump local command", w[k].c_str());
+      if (d->lcols.n >= kContactMaxCols) sf::fail("Illegal dump local command");
+      d->lcols.c[d->lcols.n++] = (unsigned char)c;
+      d->columns += (d->columns.empty() ? "" : " ") + w[k];
+    }
+    if (d->compute.empty())
+      sf::fail("Invalid dump style local without a c_ID column: the rows of a dump local are those of its compute "
+               "pair/local");
+    d->stride = contact_line_stride(d->lcols);
+  }
+  for (size_t k = 6; k < w.size() && !local; k++) {
     int c = -1;
     for (int q = 0; q < C_NCOL; q++)
       if (w[k] == kColName[q]) c = q;
@@ -492,6 +570,9 @@ void dump_modify_command(SfLammps& L, const std::vector<std::string>& w)
   DumpSet* S = set_of(L);
   Dump* d = S ? S->find(w[1]) : nullptr;
   if (!d) sf::fail("Could not find dump_modify ID %s", w[1].c_str());
+  if (d->local)
+    sf::fail("dump_modify %s on a dump local is not supported by this engine (its rows come in the engine's order: atom "
+             "index, then partner tag)", w.size() > 2 ? w[2].c_str() : "");
   for (size_t k = 2; k < w.size(); k += 2) {
     if (w[k] != "sort")
       sf::fail("dump_modify %s is not supported by this engine (only `sort id` is)", w[k].c_str());
@@ -551,6 +632,47 @@ void dump_write_due(SfLammps& L)
 void dump_drain(SfLammps& L)
 {
   if (DumpSet* S = set_of(L)) S->drain();
+}
+
+bool dump_uses_compute(const SfLammps& L, const std::string& id)
+{
+  const DumpSet* S = set_of(L);
+  if (!S) return false;
+  for (const auto& d : S->dumps)
+    if (d->local && d->compute == id) return true;
+  return false;
+}
+
+size_t dump_local_cost(SfLammps& L, const ContactRows& R, double* ms)
+{
+  *ms = 0.0;
+  if (R.n <= 0) return 0;
+  hipStream_t s = L.eng.stream();
+  ContactCols cols;
+  cols.n = 0;
+  cols.c[cols.n++] = kContactIndex;
+  for (int c = 0; c < CV_COUNT; c++) cols.c[cols.n++] = (unsigned char)c;
+  const int stride = contact_line_stride(cols);
+  hipEvent_t ev[4];
+  for (hipEvent_t& e : ev) SF_HIP(hipEventCreate(&e));
+  struct EvGuard {
+    hipEvent_t* ev;
+    ~EvGuard()
+    {
+      for (int k = 0; k < 4; k++) (void)hipEventDestroy(ev[k]);
+    }
+  } guard{ev};
+  Pipeline pipe;
+  unsigned long long small[4] = {0, 0, 0, 0};
+  const size_t total = pipe.run(R.n, stride, false, s, [&](char* slots, unsigned long long* len, unsigned long long*) {
+    contact_lines_launch(R, cols, stride, slots, len, s);
+  }, small, ev);
+  SF_HIP(hipStreamSynchronize(s));
+  float a = 0.f, b = 0.f;
+  SF_HIP(hipEventElapsedTime(&a, ev[0], ev[1]));
+  SF_HIP(hipEventElapsedTime(&b, ev[2], ev[3]));
+  *ms = (double)a + (double)b;
+  return total;
 }
 
 }  // namespace sf

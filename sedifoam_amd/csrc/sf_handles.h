@@ -35,11 +35,15 @@ struct SfLammps {
   // the `restart` schedule, the fix IDs of the walls and the wall rows of a restart file (sf_restart.hip); opaque like halo
   void* restart = nullptr;
   void (*restart_delete)(void*) = nullptr;
+  // the `compute pair/local` commands and the device scratch of their rows (sf_contacts.hip); opaque like halo
+  void* computes = nullptr;
+  void (*computes_delete)(void*) = nullptr;
   ~SfLammps()
   {
     if (restart && restart_delete) restart_delete(restart);
     if (thermo && thermo_delete) thermo_delete(thermo);   // (closes the log and screen files)
     if (dumps && dumps_delete) dumps_delete(dumps);   // (drains the writer: the frames are in their files)
+    if (computes && computes_delete) computes_delete(computes);   // (after the dumps, whose frames read its rows)
     if (halo && halo_delete) halo_delete(halo);
   }
 };

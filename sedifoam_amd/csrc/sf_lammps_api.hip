@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/sedifoam_amd.h"
+#include "sf_contacts.h"
 #include "sf_dump.h"
 #include "sf_env.h"
 #include "sf_handles.h"
@@ -573,6 +574,8 @@ void command(SfLammps& L, const std::string& line)
     sf::dump_modify_command(L, w);
   } else if (c == "undump") {
     sf::undump_command(L, w);
+  } else if (c == "compute" || c == "uncompute") {
+    sf::compute_command(L, w);   // compute pair/local (gran/local): the rows of dump local (sf_contacts.hip)
   } else if (c == "processors") {
     // [3P] processors px py pz (`*` = chosen by LAMMPS); must come before the box is created, like in LAMMPS
     if (w.size() < 4) sf::fail("Illegal processors command");

@@ -140,6 +140,32 @@ class Lammps:
         check(self.L.sf_lammps_restart_cost(self.ptr, int(timing), _p(out)))
         return tuple(out[:3])
 
+    def contacts(self, group="all"):
+        """the contact network now (what a `dump local` frame of a compute pair/local on `group` would hold, in its order):
+        one row per touching pair of two atoms of the group, tag1 < tag2, evaluated from the current state with
+        shearupdate = false.  dict of arrays: tag1, tag2, dist, force (signed normal force, repulsive > 0), f[n, 3] (the
+        normal force on tag1), fs[n, 3] (the tangential force on tag1), fsmag.  Passive: the run goes on with the same bits"""
+        g = group.encode()
+        n = check(self.L.sf_lammps_get_contacts(self.ptr, g, 0, None, None, None))
+        t1 = np.zeros(n, np.int32); t2 = np.zeros(n, np.int32); val = np.zeros((n, 9))
+        if n:
+            m = check(self.L.sf_lammps_get_contacts(self.ptr, g, n, _p(t1), _p(t2), _p(val)))
+            assert m == n
+        return dict(tag1=t1, tag2=t2, dist=val[:, 0].copy(), force=val[:, 1].copy(), f=val[:, 2:5].copy(),
+                    fs=val[:, 5:8].copy(), fsmag=val[:, 8].copy())
+
+    def contact_launches(self):
+        """kernel launches made for contact rows so far"""
+        n = C.c_longlong()
+        check(self.L.sf_lammps_contact_launches(self.ptr, C.byref(n)))
+        return n.value
+
+    def contact_cost(self, group="all"):
+        """(GPU ms of count + scan + rows, GPU ms of the text of every column, rows) of one evaluation now"""
+        out = np.zeros(3)
+        check(self.L.sf_lammps_contact_cost(self.ptr, group.encode(), _p(out)))
+        return float(out[0]), float(out[1]), int(out[2])
+
     def set_molecule(self, tags, mol):
         """molecule IDs of the atoms with these tags (what `read_data FILE fix ID NULL Molecules` reads from a file)"""
         t, m = _i32(tags), _i32(mol)
