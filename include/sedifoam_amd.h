@@ -139,6 +139,19 @@ int sf_lammps_contact_launches(void *ptr, long long *launches);
 /* measurement (tools/contact_cost.py): out3 = {GPU ms of count + scan + rows, GPU ms of the text of every column (lines +
  * scan + compact), rows} of one evaluation now, from HIP events; nothing is written */
 int sf_lammps_contact_cost(void *ptr, const char *group, double *out3);
+/* the per-atom computes (the script commands `compute ID group stress/atom | contact/atom | ke/atom | erotate/sphere/atom`;
+ * `dump ID group custom N FILE ... c_ID ... c_ID[k] ...` writes the same values as text): the values of compute `id` for
+ * every owned atom, evaluated from the state as it stands -- x, v, omega, the shear history sf_dem_get_history returns --
+ * with shearupdate = false; nothing is stored and the run goes on with the same bits.  values is row-major [max][*ncols]
+ * in atom-index order (tag[] says which atom a row is), *ncols = 6 for stress/atom (xx yy zz xy xz yz, stress x volume,
+ * LAMMPS' sign) and 1 otherwise; atoms outside the compute's group read 0.  Returns the number of owned atoms, or -1
+ * (sf_last_error); with max smaller than that (0, to size the arrays) nothing is written, the count and *ncols are still
+ * returned.  A compute is evaluated once per step however many dumps and queries name it. */
+long long sf_lammps_compute_atom(void *ptr, const char *id, long long max, int *tag, double *values, int *ncols);
+/* kernel launches made for per-atom computes so far (0 for a run in which no dump names one and no query is made) */
+int sf_lammps_compute_atom_launches(void *ptr, long long *launches);
+/* measurement (tools/compute_atom_cost.py): GPU ms of one fresh evaluation of compute `id` now, from HIP events */
+int sf_lammps_compute_atom_cost(void *ptr, const char *id, double *ms);
 /* library.h:61-63 (particle injection / removal; tag[] is double in the reference) */
 int sf_lammps_create_particle(void *ptr, int npAdd, const double *position, const double *tag,
                               double diameter, double rho, int type, const double *vel);

@@ -1,0 +1,421 @@
+// sf_compute_atom.hip -- the per-atom computes ([3P] LAMMPS names and definitions):
+//   compute ID group stress/atom [NULL] [ke] [pair] [virial] [fix] [bond] [angle] [dihedral] [improper] [kspace]
+//       six columns xx yy zz xy xz yz in stress x volume units, LAMMPS' sign (nktv2p = mvv2e = 1):
+//       s_ab(i) = -( [ke] m_i v_a v_b + [pair] sum_j 1/2 del_a F_b ),  del = x_i - x_j with the partner moved to the periodic
+//       image the list word names, F the pair style's force on i from j (normal + tangential, the `fix freeze` meff
+//       override included): the ev_tally_xyz half share under newton off, exactly the summand of k_thermo_virial
+//       (sf_thermo.hip), so that the sum over all atoms is thermo's W and kinetic terms.  No keyword: ke and pair.  fix,
+//       bond ... kspace add nothing: no fix here tallies a virial; walls, cohesion, drag and gravity are not in it.
+//   compute ID group contact/atom          the partners j (of any group) with rsq < (radi + radj)^2
+//   compute ID group ke/atom               1/2 m v^2
+//   compute ID group erotate/sphere/atom   1/2 (0.4 m r^2) omega^2
+// The group selects the atoms that get a value; atoms outside it read 0.  Like compute pair/local (sf_contacts.hip) a
+// value is evaluated from the state AT THE MOMENT OF THE OUTPUT -- the x v omega a dump custom frame shows, the shear
+// history sf_dem_get_history returns -- with shearupdate = false, and nothing is stored back.  (LAMMPS tallies vatom inside
+// the step's force evaluation, with the half-step velocities; at `run 0` the two coincide.)
+//
+// One launch per evaluation, one lane per owned atom, field-major stores val[c][i]; no atomics, no LDS, no
+// floating-point reduction across lanes: the same state gives the same bits.  An evaluation is kept with the step it was
+// made at and shared by every dump and query of that step.
+#include <algorithm>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/sedifoam_amd.h"
+#include "sf_compute_atom.h"
+#include "sf_compute_parse.h"
+#include "sf_dem_dispatch.h"
+#include "sf_handles.h"
+
+namespace sf {
+namespace {
+
+__device__ __forceinline__ Vec3 av3(const double4& a) { return {a.x, a.y, a.z}; }
+
+// The neighbour loop of k_thermo_virial (sf_thermo.hip) with shearupdate = false, keeping the atom's own six sums: the
+// same list words (root + image code, or plain index with ghost atoms), the pair's history from this side's slot where
+// the word carries kOwnBit, from the owner's slot negated where it does not, zero without the touch bit.
+template <int STYLE>
+__global__ __launch_bounds__(256) void k_atom_virial(DemPtrs P, StepParams S, const int* mask, int groupbit, int ke, int pair,
+                                                     double* val)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= S.nlocal) return;
+  const size_t n = (size_t)S.nlocal, cap = (size_t)S.cap;
+  double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (mask[i] & groupbit) {
+    const double4 xi4 = P.xr_in[i], vi4 = P.vm_in[i], wi4 = P.om_in[i];
+    const Vec3 xi = av3(xi4), vi = av3(vi4), wi = av3(wi4);
+    const double radi = xi4.w, mi = vi4.w;
+    const int nn = pair ? P.numneigh[i] : 0;
+    for (int s = 0; s < nn; s++) {
+      const int jraw = P.neigh[(size_t)s * cap + i];
+      const int j = neigh_index(jraw, S.roots);
+      const bool own = (jraw & kOwnBit) != 0;
+      double4 xj4 = P.xr_in[j];
+      if (S.roots && own) shift_to_image(xj4, jraw, S.prd);
+      const Vec3 del = xi - av3(xj4);
+      const double rsq = dot(del, del);
+      const double radj = xj4.w;
+      const double radsum = radi + radj;
+      if (!(rsq < radsum * radsum)) continue;
+      const double4 vj4 = P.vm_in[j], wj4 = P.om_in[j];
+      Vec3 sh = {0.0, 0.0, 0.0};
+      if (jraw & kTouchBit) {
+        if (own) {
+          const double* hin = P.shear_in + (size_t)(3 * s) * cap;
+          sh = {hin[i], hin[cap + i], hin[2 * cap + i]};
+        } else {   // the owner's value, seen from this side
+          const double* src = P.shear_in + (size_t)(3 * ((jraw >> kIdxBits) & 31)) * cap + (size_t)(jraw & kIdxMask);
+          sh = {-src[0], -src[cap], -src[2 * cap]};
+        }
+      }
+      ContactIn c;
+      c.del = del;
+      c.rsq = rsq;
+      sf_sqrt_rsqrt(rsq, c.r, c.rinv);
+      c.vr = vi - av3(vj4);
+      c.wsum = {radi * wi.x + radj * wj4.x, radi * wi.y + radj * wj4.y, radi * wi.z + radj * wj4.z};
+      const double mj = vj4.w;
+      const PairScales m = pair_scales(mi, mj, radi, radj, c.r);
+      c.overlap = m.overlap;
+      c.meff = m.meff;
+      c.reff = m.reff;
+      if (S.freeze_bit) {   // pair_gran_hertzFix_history.cpp:188-189
+        if (wi4.w != 0.0) c.meff = mj;
+        if (wj4.w != 0.0) c.meff = mi;
+      }
+      ContactOut o;
+      gran_history_law<STYLE>(S.gran, S.dt, false, c, sh, o);
+      v[0] += 0.5 * del.x * o.F.x;
+      v[1] += 0.5 * del.y * o.F.y;
+      v[2] += 0.5 * del.z * o.F.z;
+      v[3] += 0.5 * del.x * o.F.y;
+      v[4] += 0.5 * del.x * o.F.z;
+      v[5] += 0.5 * del.y * o.F.z;
+    }
+    if (ke) {
+      v[0] += mi * vi.x * vi.x;
+      v[1] += mi * vi.y * vi.y;
+      v[2] += mi * vi.z * vi.z;
+      v[3] += mi * vi.x * vi.y;
+      v[4] += mi * vi.x * vi.z;
+      v[5] += mi * vi.y * vi.z;
+    }
+#pragma unroll
+    for (int c = 0; c < 6; c++) v[c] = -v[c];
+  }
+#pragma unroll
+  for (int c = 0; c < 6; c++) val[(size_t)c * n + i] = v[c];
+}
+
+// the same walk, gathering only what the touch test needs: the partner's record
+__global__ __launch_bounds__(256) void k_atom_contacts(DemPtrs P, StepParams S, const int* mask, int groupbit, double* val)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= S.nlocal) return;
+  int count = 0;
+  if (mask[i] & groupbit) {
+    const size_t cap = (size_t)S.cap;
+    const double4 xi4 = P.xr_in[i];
+    const Vec3 xi = av3(xi4);
+    const int nn = P.numneigh[i];
+    for (int s = 0; s < nn; s++) {
+      const int jraw = P.neigh[(size_t)s * cap + i];
+      double4 xj4 = P.xr_in[neigh_index(jraw, S.roots)];
+      if (S.roots && (jraw & kOwnBit)) shift_to_image(xj4, jraw, S.prd);
+      const Vec3 del = xi - av3(xj4);
+      const double radsum = xi4.w + xj4.w;
+      count += dot(del, del) < radsum * radsum ? 1 : 0;
+    }
+  }
+  val[i] = (double)count;
+}
+
+// rot = 0: 1/2 m v^2;  rot = 1: 1/2 (0.4 m r^2) omega^2  ([3P] ComputeERotateSphereAtom, INERTIA = 0.4)
+__global__ __launch_bounds__(256) void k_atom_kinetic(const double4* xr, const double4* vm, const double4* om, const int* mask,
+                                                      int groupbit, int rot, int n, double* val)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double e = 0.0;
+  if (mask[i] & groupbit) {
+    const double4 v = vm[i];
+    if (rot) {
+      const double4 w = om[i];
+      const double r = xr[i].w;
+      e = 0.5 * (0.4 * v.w * r * r) * (w.x * w.x + w.y * w.y + w.z * w.z);
+    } else
+      e = 0.5 * v.w * (v.x * v.x + v.y * v.y + v.z * v.z);
+  }
+  val[i] = e;
+}
+
+// ---- host side ----
+
+enum Kind { K_STRESS, K_CONTACT, K_KE, K_EROTATE };
+const char* const kStyleName[4] = {"stress/atom", "contact/atom", "ke/atom", "erotate/sphere/atom"};
+
+struct Grown {   // device scratch, grown geometrically (no allocation per frame once it has grown)
+  void* p = nullptr;
+  size_t n = 0;
+  void* get(size_t need, hipStream_t s)
+  {
+    if (need > n) {
+      if (p) {
+        SF_HIP(hipStreamSynchronize(s));
+        SF_HIP(hipFree(p));
+      }
+      n = need + need / 4 + 4096;
+      SF_HIP(hipMalloc(&p, n));
+    }
+    return p;
+  }
+  ~Grown()
+  {
+    if (p) (void)hipFree(p);
+  }
+};
+
+struct AtomCompute {
+  std::string id;
+  Kind kind = K_KE;
+  int groupbit = 1;
+  bool ke = true, pair = true;
+  Grown val;
+  // what the buffer was made at (-1: nothing)
+  long long step = -1, nbuilds = -1;
+  int nlocal = -1;
+  int ncols() const { return kind == K_STRESS ? 6 : 1; }
+};
+
+struct AtomSet {
+  std::vector<std::unique_ptr<AtomCompute>> computes;
+  long long launches = 0;
+  AtomCompute* find(const std::string& id)
+  {
+    for (auto& c : computes)
+      if (c->id == id) return c.get();
+    return nullptr;
+  }
+};
+
+AtomSet* set_of(const SfLammps& L) { return static_cast<AtomSet*>(L.atom_computes); }
+AtomSet& ensure_set(SfLammps& L)
+{
+  if (!L.atom_computes) {
+    L.atom_computes = new AtomSet();
+    L.atom_computes_delete = [](void* p) { delete static_cast<AtomSet*>(p); };
+  }
+  return *set_of(L);
+}
+
+// what an evaluation needs of the engine as it is now (checked at the compute line and at every evaluation: the pair
+// style and the fixes may have changed since)
+void refuse_unsupported(const SfLammps& L, Kind kind)
+{
+  const DemEngine& e = L.eng;
+  const char* who = kStyleName[kind];
+  if (L.world_size > 1 || L.decomposed || e.nranks() > 1 || e.decomposed())
+    fail("compute %s: one rank only (no decomposed domain)", who);
+  if (kind == K_STRESS) {
+    if (e.pair_lubricate_on())
+      fail("compute stress/atom: not with lubricate/poly in the pair style (its pair terms are not in the per-atom stress)");
+    if (e.pair_gran_style() == 0)
+      fail("compute stress/atom: no granular pair style is defined (the per-atom virial is that of the contact law)");
+    if (e.rigid_on())
+      fail("compute stress/atom: not while fix rigid/nve exists (the pair law then takes the masses of the bodies)");
+  } else if (kind == K_CONTACT) {
+    if (e.pair_gran_style() == 0 && !e.pair_lubricate_on())
+      fail("compute contact/atom: no pair style is defined (a pair style builds the neighbour list it counts in)");
+  }
+}
+
+void evaluate(SfLammps& L, AtomSet& T, AtomCompute& c)
+{
+  refuse_unsupported(L, c.kind);
+  DemEngine& e = L.eng;
+  const int n = e.nlocal();
+  hipStream_t st = e.stream();
+  double* val = static_cast<double*>(c.val.get(sizeof(double) * (size_t)c.ncols() * (size_t)std::max(n, 1), st));
+  if (n > 0) {
+    const unsigned nb = (unsigned)div_up(n, 256);
+    if (c.kind == K_KE || c.kind == K_EROTATE) {
+      k_atom_kinetic<<<nb, 256, 0, st>>>(e.d_xr(), e.d_vm(), e.d_om(), e.d_mask(), c.groupbit, c.kind == K_EROTATE ? 1 : 0, n,
+                                         val);
+    } else {
+      DemPtrs P;
+      StepParams S;
+      if (!e.contact_view(&P, &S))
+        fail("compute %s: no neighbour list yet (the contacts are those of the last force evaluation: run 0 first)",
+             kStyleName[c.kind]);
+      if (S.nlocal != n) fail("compute %s: the list does not describe the owned atoms", kStyleName[c.kind]);
+      if (c.kind == K_CONTACT) k_atom_contacts<<<nb, 256, 0, st>>>(P, S, e.d_mask(), c.groupbit, val);
+      else {
+        const int ke = c.ke ? 1 : 0, pair = c.pair ? 1 : 0;
+        const int groupbit = c.groupbit;
+        const int* mask = e.d_mask();
+        // (plain gran/hooke, GranParams::style 3, runs the Hookean instantiation: the law branches on the style itself)
+        style_dispatch(S.gran.style, [&](auto style) {
+          constexpr int ST = decltype(style)::value == 2 ? 2 : 1;
+          k_atom_virial<ST><<<nb, 256, 0, st>>>(P, S, mask, groupbit, ke, pair, val);
+        });
+      }
+    }
+    SF_HIP(hipGetLastError());
+    T.launches++;
+  }
+  c.step = e.nsteps();
+  c.nbuilds = e.nbuilds();
+  c.nlocal = n;
+}
+
+}  // namespace
+
+bool atom_compute_style(const std::string& style)
+{
+  for (const char* s : kStyleName)
+    if (style == s) return true;
+  return false;
+}
+
+void atom_compute_define(SfLammps& L, const std::vector<std::string>& w)
+{
+  auto c = std::make_unique<AtomCompute>();
+  c->id = w[1];
+  c->groupbit = L.eng.group_bit(w[2]);
+  for (int k = 0; k < 4; k++)
+    if (w[3] == kStyleName[k]) c->kind = (Kind)k;
+  if (c->kind == K_STRESS) {
+    const std::string err = parse_stress_keywords(w, 4, &c->ke, &c->pair);
+    if (!err.empty()) fail("%s", err.c_str());
+  } else if (w.size() != 4)
+    fail("Illegal compute %s command", w[3].c_str());
+  refuse_unsupported(L, c->kind);
+  ensure_set(L).computes.push_back(std::move(c));
+}
+
+int atom_compute_ncols(const SfLammps& L, const std::string& id)
+{
+  AtomSet* T = set_of(L);
+  const AtomCompute* c = T ? T->find(id) : nullptr;
+  return c ? c->ncols() : 0;
+}
+
+void atom_compute_remove(SfLammps& L, const std::string& id)
+{
+  AtomSet* T = set_of(L);
+  if (!T) return;
+  for (size_t k = 0; k < T->computes.size(); k++)
+    if (T->computes[k]->id == id) {
+      SF_HIP(hipStreamSynchronize(L.eng.stream()));   // (a frame queued on the stream may still read its buffer)
+      T->computes.erase(T->computes.begin() + k);
+      return;
+    }
+}
+
+const double* atom_compute_values(SfLammps& L, const std::string& id, int* ncols)
+{
+  AtomSet* T = set_of(L);
+  AtomCompute* c = T ? T->find(id) : nullptr;
+  if (!c) fail("Could not find compute ID %s", id.c_str());
+  const DemEngine& e = L.eng;
+  if (c->step != e.nsteps() || c->nbuilds != e.nbuilds() || c->nlocal != e.nlocal()) evaluate(L, *T, *c);
+  else refuse_unsupported(L, c->kind);
+  if (ncols) *ncols = c->ncols();
+  return static_cast<const double*>(c->val.p);
+}
+
+void atom_compute_invalidate(SfLammps& L)
+{
+  if (AtomSet* T = set_of(L))
+    for (auto& c : T->computes) c->step = -1;
+}
+
+long long atom_compute_launches(const SfLammps& L)
+{
+  const AtomSet* T = set_of(L);
+  return T ? T->launches : 0;
+}
+
+double atom_compute_cost(SfLammps& L, const std::string& id)
+{
+  AtomSet* T = set_of(L);
+  AtomCompute* c = T ? T->find(id) : nullptr;
+  if (!c) fail("Could not find compute ID %s", id.c_str());
+  hipStream_t st = L.eng.stream();
+  hipEvent_t ev[2];
+  for (hipEvent_t& e : ev) SF_HIP(hipEventCreate(&e));
+  struct EvGuard {
+    hipEvent_t* ev;
+    ~EvGuard()
+    {
+      for (int k = 0; k < 2; k++) (void)hipEventDestroy(ev[k]);
+    }
+  } guard{ev};
+  c->val.get(sizeof(double) * (size_t)c->ncols() * (size_t)std::max(L.eng.nlocal(), 1), st);   // (not in the time)
+  SF_HIP(hipEventRecord(ev[0], st));
+  evaluate(L, *T, *c);
+  SF_HIP(hipEventRecord(ev[1], st));
+  SF_HIP(hipStreamSynchronize(st));
+  float ms = 0.f;
+  SF_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+  return (double)ms;
+}
+
+}  // namespace sf
+
+namespace {
+sf::SfLammps* handle(void* p)
+{
+  if (!p) sf::fail("null engine handle");
+  return static_cast<sf::SfLammps*>(p);
+}
+}  // namespace
+
+extern "C" {
+
+long long sf_lammps_compute_atom(void* ptr, const char* id, long long max, int* tag, double* values, int* ncols)
+{
+  long long n = 0;
+  SF_API_BEGIN
+  sf::SfLammps& L = *handle(ptr);
+  if (!id) sf::fail("sf_lammps_compute_atom: null argument");
+  int nc = 0;
+  const double* d_val = sf::atom_compute_values(L, id, &nc);
+  if (ncols) *ncols = nc;
+  n = L.eng.nlocal();
+  if (n > 0 && n <= max) {
+    if (!tag || !values) sf::fail("sf_lammps_compute_atom: null argument");
+    hipStream_t st = L.eng.stream();
+    std::vector<double> cols((size_t)nc * (size_t)n);
+    SF_HIP(hipMemcpyAsync(tag, L.eng.d_tag(), sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipMemcpyAsync(cols.data(), d_val, sizeof(double) * cols.size(), hipMemcpyDeviceToHost, st));
+    SF_HIP(hipStreamSynchronize(st));
+    for (long long r = 0; r < n; r++)   // field-major on the device, row-major for the caller
+      for (int c = 0; c < nc; c++) values[(size_t)nc * (size_t)r + c] = cols[(size_t)c * (size_t)n + (size_t)r];
+  }
+  SF_API_END(n)
+}
+
+int sf_lammps_compute_atom_launches(void* ptr, long long* launches)
+{
+  SF_API_BEGIN
+  if (!launches) sf::fail("sf_lammps_compute_atom_launches: null argument");
+  *launches = sf::atom_compute_launches(*handle(ptr));
+  SF_API_END(0)
+}
+
+int sf_lammps_compute_atom_cost(void* ptr, const char* id, double* ms)
+{
+  SF_API_BEGIN
+  if (!id || !ms) sf::fail("sf_lammps_compute_atom_cost: null argument");
+  *ms = sf::atom_compute_cost(*handle(ptr), id);
+  SF_API_END(0)
+}
+
+}  // extern "C"

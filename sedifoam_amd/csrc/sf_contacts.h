@@ -34,6 +34,8 @@ struct ContactCols {   // the columns of a text line: ContactValue or kContactIn
 
 // `compute` / `uncompute`: true when the word was one of the two
 bool compute_command(SfLammps& L, const std::vector<std::string>& w);
+// is `id` a compute pair/local?
+bool pair_local_exists(const SfLammps& L, const std::string& id);
 // the values and the group of compute `id` (fails with LAMMPS' wording when there is none)
 void compute_lookup(const SfLammps& L, const std::string& id, std::vector<unsigned char>* values, int* groupbit);
 // count + scan + rows on the engine's stream; synchronises it once (the row count).  ms != nullptr: the GPU time of the
@@ -45,7 +47,7 @@ void contact_lines_launch(const ContactRows& R, const ContactCols& cols, int str
 int contact_line_stride(const ContactCols& cols);
 long long contact_launches(const SfLammps& L);
 
-// sf_dump.hip: does a `dump local` name this compute?
+// sf_dump.hip: does a dump name this compute (a dump local its pair/local, a dump custom a per-atom compute)?
 bool dump_uses_compute(const SfLammps& L, const std::string& id);
 // sf_dump.hip (tools/contact_cost.py): every column of every row as text through the dump pipeline, nothing written;
 // returns the byte count and the GPU time of lines + scan + compact

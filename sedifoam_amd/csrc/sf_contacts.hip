@@ -33,6 +33,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/sedifoam_amd.h"
+#include "sf_compute_atom.h"
 #include "sf_contacts.h"
 #include "sf_dem_dispatch.h"
 #include "sf_dump_fmt.h"
@@ -313,8 +314,14 @@ bool compute_command(SfLammps& L, const std::vector<std::string>& w)
     if (w.size() != 2) fail("Illegal uncompute command");
     ContactSet* S = set_of(L);
     Compute* c = S ? S->find(w[1]) : nullptr;
-    if (!c) fail("Could not find compute ID to delete");   // [3P] Modify::delete_compute
-    if (dump_uses_compute(L, w[1])) fail("uncompute %s: a dump local still uses this compute (undump it first)", w[1].c_str());
+    const bool per_atom = !c && atom_compute_ncols(L, w[1]) > 0;   // (one ID space: sf_compute_atom.hip holds the others)
+    if (!c && !per_atom) fail("Could not find compute ID to delete");   // [3P] Modify::delete_compute
+    if (dump_uses_compute(L, w[1]))
+      fail("uncompute %s: a dump %s still uses this compute (undump it first)", w[1].c_str(), per_atom ? "custom" : "local");
+    if (per_atom) {
+      atom_compute_remove(L, w[1]);
+      return true;
+    }
     S->computes.erase(S->computes.begin() + (c - S->computes.data()));
     return true;
   }
@@ -324,12 +331,18 @@ bool compute_command(SfLammps& L, const std::vector<std::string>& w)
   if (style == "cohe/local")
     fail("compute cohe/local is not built (fix cohesive is a fix and has no single(); the reference's own code behind it "
          "never terminates)");
-  if (style != "pair/local" && style != "gran/local")
-    fail("Invalid compute style %s (this engine has compute pair/local, also under the name gran/local)", style.c_str());
+  const bool per_atom = atom_compute_style(style);
+  if (style != "pair/local" && style != "gran/local" && !per_atom)
+    fail("Invalid compute style %s (this engine has compute pair/local, also under the name gran/local, and the per-atom "
+         "computes stress/atom, contact/atom, ke/atom and erotate/sphere/atom)", style.c_str());
   Compute c;
   c.id = w[1];
   c.groupbit = L.eng.group_bit(w[2]);
-  if (set_of(L) && set_of(L)->find(c.id)) fail("Reuse of compute ID");
+  if ((set_of(L) && set_of(L)->find(c.id)) || atom_compute_ncols(L, c.id) > 0) fail("Reuse of compute ID");
+  if (per_atom) {
+    atom_compute_define(L, w);   // (sf_compute_atom.hip)
+    return true;
+  }
   if (w.size() < 5) fail("Illegal compute pair/local command");
   refuse_unsupported(L, "compute pair/local");
   for (size_t k = 4; k < w.size(); k++) {
@@ -348,10 +361,18 @@ bool compute_command(SfLammps& L, const std::vector<std::string>& w)
   return true;
 }
 
+bool pair_local_exists(const SfLammps& L, const std::string& id)
+{
+  ContactSet* S = set_of(L);
+  return S && S->find(id);
+}
+
 void compute_lookup(const SfLammps& L, const std::string& id, std::vector<unsigned char>* values, int* groupbit)
 {
   ContactSet* S = set_of(L);
   const Compute* c = S ? S->find(id) : nullptr;
+  if (!c && atom_compute_ncols(L, id) > 0)   // [3P] DumpLocal::parse_fields
+    fail("Dump local compute does not compute local info: %s is a per-atom compute (dump custom prints it)", id.c_str());
   if (!c) fail("Could not find dump local compute ID %s", id.c_str());
   if (values) *values = c->values;
   if (groupbit) *groupbit = c->groupbit;

@@ -14,6 +14,10 @@
 // `dump ID group local N file index c_ID[k] ...` ([3P] DumpLocal) goes the same way with another first launch: the rows of
 // the compute pair/local it names are evaluated (sf_contacts.hip: count, scan, rows) and k_contact_lines, one lane per row,
 // fills the slots.  Schedule, `*`, undump, the step-0 frame and the writer are the shared code below.
+//
+// `c_ID` / `c_ID[k]` columns of a dump custom ([3P] DumpCustom::parse_fields) are the per-atom computes of
+// sf_compute_atom.hip: a frame asks for their values (evaluated once per step, whoever asks) and k_dump_lines prints them
+// as "%g " from the field-major device columns, between the other columns, sorted or not.
 #include <algorithm>
 #include <climits>
 #include <condition_variable>
@@ -31,6 +35,8 @@
 
 #include "../../include/sedifoam_amd.h"
 #include "sf_common.h"
+#include "sf_compute_atom.h"
+#include "sf_compute_parse.h"
 #include "sf_contacts.h"
 #include "sf_dump.h"
 #include "sf_dump_fmt.h"
@@ -49,7 +55,12 @@ const char* const kColName[C_NCOL] = {"id", "type", "mass", "diameter", "radius"
 constexpr int kMaxCols = 64;
 struct Cols {
   int n;
-  unsigned char c[kMaxCols];
+  unsigned char c[kMaxCols];   // a Col, or C_NCOL + e: column e of XCols
+};
+// the c_ID / c_ID[k] columns of a frame: one device column of a per-atom compute each, indexed by atom
+constexpr int kMaxXCols = 24;
+struct XCols {
+  const double* p[kMaxXCols];
 };
 
 __device__ __forceinline__ double col_value(int c, const double4& x, const double4& v, const double4& w,
@@ -82,7 +93,7 @@ __device__ __forceinline__ double col_value(int c, const double4& x, const doubl
 __global__ __launch_bounds__(256) void k_dump_lines(const double4* xr, const double4* vm, const double4* om,
                                                     const double4* force, const double4* torque, const int* tag,
                                                     const int* type, const int* mask, int n, int groupbit, Cols cols,
-                                                    int sorted, long long nslots, int stride, char* slots,
+                                                    XCols xcols, int sorted, long long nslots, int stride, char* slots,
                                                     unsigned long long* len, unsigned long long* count,
                                                     unsigned long long* err)
 {
@@ -108,6 +119,7 @@ __global__ __launch_bounds__(256) void k_dump_lines(const double4* xr, const dou
     const int c = cols.c[k];
     if (c == C_ID) p += fmt::format_d(tag[i], p);
     else if (c == C_TYPE) p += fmt::format_d(type[i], p);
+    else if (c >= C_NCOL) p += fmt::format_g(xcols.p[c - C_NCOL][i], p);
     else p += fmt::format_g(col_value(c, x, v, w, f, t), p);
     *p++ = ' ';
   }
@@ -222,6 +234,9 @@ struct Dump {
   bool local = false;    // dump local: the rows of `compute` (a compute pair/local), columns lcols
   std::string compute;
   ContactCols lcols{};
+  // dump custom: the c_ columns -- column xcol[e] (0-based) of the per-atom compute xid[e] (sf_compute_atom.hip)
+  std::vector<std::string> xid;
+  std::vector<int> xcol;
   bool gather = false;   // one file written by rank 0 on more than one rank
   long long last = -1;   // the step of the last frame ([3P] Output::last_dump)
   FILE* fp = nullptr;    // the single file (not `*`), opened and truncated by the dump command
@@ -381,10 +396,20 @@ void write_frame(SfLammps& L, DumpSet& S, Dump& d)
   } else if (n > 0 && nslots > 0) {
     const int groupbit = d.groupbit, sorted = d.sort ? 1 : 0, stride = d.stride;
     const Cols cols = d.cols;
+    XCols xcols{};
+    if (!d.xid.empty() && (L.world_size > 1 || L.decomposed || e.nranks() > 1 || e.decomposed()))
+      fail("dump %s: c_ columns on one rank only (no decomposed domain)", d.id.c_str());
+    for (size_t k = 0; k < d.xid.size(); k++) {
+      // (evaluated on this stream, at most once per step however many columns, dumps and queries name the compute)
+      int nc = 0;
+      const double* val = atom_compute_values(L, d.xid[k], &nc);
+      if (d.xcol[k] >= nc) fail("dump %s: compute %s has %d columns", d.id.c_str(), d.xid[k].c_str(), nc);
+      xcols.p[k] = val + (size_t)d.xcol[k] * (size_t)n;
+    }
     total = d.pipe.run(nslots, stride, d.sort, s, [&](char* slots, unsigned long long* len, unsigned long long* small) {
       k_dump_lines<<<(n + 255) / 256, 256, 0, s>>>(e.d_xr(), e.d_vm(), e.d_om(), e.d_force(), e.d_torque(), e.d_tag(),
-                                                   e.d_type(), e.d_mask(), n, groupbit, cols, sorted, nslots, stride,
-                                                   slots, len, small, small + 1);
+                                                   e.d_type(), e.d_mask(), n, groupbit, cols, xcols, sorted, nslots,
+                                                   stride, slots, len, small, small + 1);
     }, d.h_small);
     natoms = d.h_small[1];
     if (d.h_small[2])
@@ -548,6 +573,27 @@ void dump_command(SfLammps& L, const std::vector<std::string>& w)
     int c = -1;
     for (int q = 0; q < C_NCOL; q++)
       if (w[k] == kColName[q]) c = q;
+    if (c < 0 && w[k].compare(0, 2, "c_") == 0) {
+      // [3P] DumpCustom::parse_fields: c_ID names a per-atom vector, c_ID[k] a column of a per-atom array
+      std::string id;
+      long idx = 0;
+      const std::string err = parse_compute_column(w[k], "custom", &id, &idx);
+      if (!err.empty()) sf::fail("%s", err.c_str());
+      const int nc = atom_compute_ncols(L, id);
+      if (nc == 0 && pair_local_exists(L, id))
+        sf::fail("Dump custom compute does not compute per-atom info: %s is a compute pair/local (dump local prints its "
+                 "rows)", id.c_str());
+      if (nc == 0) sf::fail("Could not find dump custom compute ID %s", id.c_str());
+      if (idx == 0 && nc != 1) sf::fail("Dump custom compute does not compute per-atom vector: %s", w[k].c_str());
+      if (idx > 0 && nc == 1) sf::fail("Dump custom compute does not compute per-atom array: %s", w[k].c_str());
+      if (idx > nc) sf::fail("Dump custom compute vector is accessed out-of-range: %s", w[k].c_str());
+      if (L.world_size > 1 || L.decomposed || L.eng.nranks() > 1 || L.eng.decomposed())
+        sf::fail("dump custom: c_ columns on one rank only (no decomposed domain)");
+      if ((int)d->xid.size() >= kMaxXCols) sf::fail("dump custom: more than %d c_ columns", kMaxXCols);
+      c = C_NCOL + (int)d->xid.size();
+      d->xid.push_back(id);
+      d->xcol.push_back(idx > 0 ? (int)idx - 1 : 0);
+    }
     if (c < 0) sf::fail("Invalid attribute %s in dump custom command", w[k].c_str());
     if (d->cols.n >= kMaxCols) sf::fail("Illegal dump custom command");
     d->cols.c[d->cols.n++] = (unsigned char)c;
@@ -639,7 +685,7 @@ bool dump_uses_compute(const SfLammps& L, const std::string& id)
   const DumpSet* S = set_of(L);
   if (!S) return false;
   for (const auto& d : S->dumps)
-    if (d->local && d->compute == id) return true;
+    if ((d->local && d->compute == id) || std::find(d->xid.begin(), d->xid.end(), id) != d->xid.end()) return true;
   return false;
 }
 

@@ -38,12 +38,16 @@ struct SfLammps {
   // the `compute pair/local` commands and the device scratch of their rows (sf_contacts.hip); opaque like halo
   void* computes = nullptr;
   void (*computes_delete)(void*) = nullptr;
+  // the per-atom computes and their device buffers (sf_compute_atom.hip); opaque like halo
+  void* atom_computes = nullptr;
+  void (*atom_computes_delete)(void*) = nullptr;
   ~SfLammps()
   {
     if (restart && restart_delete) restart_delete(restart);
     if (thermo && thermo_delete) thermo_delete(thermo);   // (closes the log and screen files)
     if (dumps && dumps_delete) dumps_delete(dumps);   // (drains the writer: the frames are in their files)
     if (computes && computes_delete) computes_delete(computes);   // (after the dumps, whose frames read its rows)
+    if (atom_computes && atom_computes_delete) atom_computes_delete(atom_computes);   // (likewise)
     if (halo && halo_delete) halo_delete(halo);
   }
 };

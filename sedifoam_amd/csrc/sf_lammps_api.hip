@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/sedifoam_amd.h"
+#include "sf_compute_atom.h"
 #include "sf_contacts.h"
 #include "sf_dump.h"
 #include "sf_env.h"
@@ -497,6 +498,7 @@ void command(SfLammps& L, const std::string& line)
   std::vector<std::string> w = split(line);
   if (w.empty()) return;
   const std::string& c = w[0];
+  sf::atom_compute_invalidate(L);   // (a command may change the state at an unchanged step: `velocity`, `pair_style`, a fix)
   if (sf::thermo_command(L, w)) return;   // thermo, thermo_style, thermo_modify, log, echo (sf_thermo.hip)
   if (c == "units") {
     if (w.size() != 2 || (w[1] != "lj" && w[1] != "si")) sf::fail("units %s not supported (lj | si: nktv2p = 1)", w.size() > 1 ? w[1].c_str() : "");
@@ -575,7 +577,9 @@ void command(SfLammps& L, const std::string& line)
   } else if (c == "undump") {
     sf::undump_command(L, w);
   } else if (c == "compute" || c == "uncompute") {
-    sf::compute_command(L, w);   // compute pair/local (gran/local): the rows of dump local (sf_contacts.hip)
+    // compute pair/local (gran/local): the rows of dump local (sf_contacts.hip); the per-atom computes behind the c_ columns
+    // of dump custom (sf_compute_atom.hip)
+    sf::compute_command(L, w);
   } else if (c == "processors") {
     // [3P] processors px py pz (`*` = chosen by LAMMPS); must come before the box is created, like in LAMMPS
     if (w.size() < 4) sf::fail("Illegal processors command");
@@ -902,6 +906,7 @@ int sf_lammps_create_particle(void* ptr, int npAdd, const double* position, cons
   SF_API_BEGIN
   SfLammps* L = H(ptr);
   if (L->eng.rigid_on()) sf::fail("lammps_create_particle: not while fix rigid/nve exists (its bodies are fixed sets of atoms)");
+  sf::atom_compute_invalidate(*L);
   L->eng.create_particles(npAdd, position, tag, diameter, rho, type, vel);
   if (L->decomposed) {   // library.cpp:470-473 (collective: every rank calls, possibly with npAdd = 0)
     recount_atoms(*L);
@@ -915,6 +920,7 @@ int sf_lammps_delete_particle(void* ptr, const int* deleteList, int nDelete)
   SF_API_BEGIN
   SfLammps* L = H(ptr);
   if (L->eng.rigid_on()) sf::fail("lammps_delete_particle: not while fix rigid/nve exists (its bodies are fixed sets of atoms)");
+  sf::atom_compute_invalidate(*L);
   L->eng.delete_particles(deleteList, nDelete);
   if (L->decomposed) {   // library.cpp:527-537: collective counts; every rank deletes the listed atoms it owns
     recount_atoms(*L);
@@ -927,6 +933,7 @@ int sf_dem_create_atoms(void* ptr, int n, const double* x, const double* v, cons
                         const double* diameter, const double* density, const int* tag, const int* type)
 {
   SF_API_BEGIN
+  sf::atom_compute_invalidate(*H(ptr));
   H(ptr)->eng.create_atoms(n, x, v, omega, diameter, density, tag, type);
   SF_API_END(0)
 }

@@ -166,6 +166,32 @@ class Lammps:
         check(self.L.sf_lammps_contact_cost(self.ptr, group.encode(), _p(out)))
         return float(out[0]), float(out[1]), int(out[2])
 
+    def compute_atom(self, cid):
+        """the values of the per-atom compute `cid` (stress/atom: [n, 6] in the order xx yy zz xy xz yz; contact/atom,
+        ke/atom, erotate/sphere/atom: [n]) now, sorted by tag like get_state(); atoms outside the compute's group read 0.
+        What a `dump custom` column c_ID / c_ID[k] written at this moment holds.  Passive: the run goes on with the same bits"""
+        cid = str(cid).encode()
+        nc = C.c_int()
+        n = check(self.L.sf_lammps_compute_atom(self.ptr, cid, 0, None, None, C.byref(nc)))
+        tag = np.zeros(n, np.int32); val = np.zeros((n, max(nc.value, 1)))
+        if n:
+            m = check(self.L.sf_lammps_compute_atom(self.ptr, cid, n, _p(tag), _p(val), C.byref(nc)))
+            assert m == n
+        val = val[np.argsort(tag, kind="stable")]
+        return val if nc.value > 1 else val[:, 0].copy()
+
+    def compute_atom_launches(self):
+        """kernel launches made for per-atom computes so far"""
+        n = C.c_longlong()
+        check(self.L.sf_lammps_compute_atom_launches(self.ptr, C.byref(n)))
+        return n.value
+
+    def compute_atom_cost(self, cid):
+        """GPU ms of one fresh evaluation of the per-atom compute `cid` now"""
+        ms = C.c_double()
+        check(self.L.sf_lammps_compute_atom_cost(self.ptr, str(cid).encode(), C.byref(ms)))
+        return ms.value
+
     def set_molecule(self, tags, mol):
         """molecule IDs of the atoms with these tags (what `read_data FILE fix ID NULL Molecules` reads from a file)"""
         t, m = _i32(tags), _i32(mol)
