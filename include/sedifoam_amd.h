@@ -67,7 +67,9 @@ int sf_lammps_file(void *ptr, const char *path);
  * the reference's in.lammps files use: units, atom_style sphere, atom_modify, boundary, newton,
  * communicate, processors, read_data (or sf_dem_create_atoms), neighbor, neigh_modify, pair_style {gran/hertzFix/history,
  * gran/hooke/history, lubricate/poly, hybrid/overlay}, pair_coeff, timestep, velocity all set,
- * fix {nve/sphere, gravity, fdrag, freeze, cohesive, wall/gran and wall/granFix ({x,y,z}plane | zcylinder, wiggle | shear)},
+ * fix {nve/sphere, gravity, fdrag, freeze, cohesive, wall/gran and wall/granFix ({x,y,z}plane | zcylinder, wiggle | shear),
+ * ave/chunk}, unfix (of a fix ave/chunk), compute {pair/local, stress/atom, contact/atom, ke/atom, erotate/sphere/atom,
+ * chunk/atom bin/1d|2d|3d}, uncompute,
  * group {type, subtract, union, intersect}, run, dump custom, thermo / thermo_style / thermo_modify, units, log,
  * echo; restart is accepted without effect.  argv: -screen none|stdout|FILE and -log none|FILE (default none, see
  * INTEGRATION.md).
@@ -152,6 +154,25 @@ long long sf_lammps_compute_atom(void *ptr, const char *id, long long max, int *
 int sf_lammps_compute_atom_launches(void *ptr, long long *launches);
 /* measurement (tools/compute_atom_cost.py): GPU ms of one fresh evaluation of compute `id` now, from HIP events */
 int sf_lammps_compute_atom_cost(void *ptr, const char *id, double *ms);
+/* binned profiles (the script commands `compute ID group chunk/atom bin/1d|bin/2d|bin/3d dim origin delta ... units box`
+ * -- a per-atom compute: c_ID in dump custom and sf_lammps_compute_atom return the chunk IDs -- and `fix ID group
+ * ave/chunk Nevery Nrepeat Nfreq chunkID vx vy vz fx fy fz density/number density/mass c_ID c_ID[k] ... [norm all|sample|
+ * none] [ave one|running] [file NAME] [overwrite] [title1|2|3 STRING] [format STRING]`, `unfix ID`): the latest output of
+ * fix `id`.  *step its step, *ndim the binned dimensions, *nvalues the value columns; coord row-major [max][*ndim] (the
+ * centres of the layers), count [max] (Ncount), values row-major [max][*nvalues], chunk 1 first.  Returns the number of
+ * chunks, or -1 (sf_last_error; also before the first output); with max smaller than that (0, to size the arrays) nothing
+ * is written to the arrays, *step, *ndim and *nvalues are still returned. */
+long long sf_lammps_ave_chunk(void *ptr, const char *id, long long max, long long *step, int *ndim, int *nvalues,
+                              double *coord, double *count, double *values);
+/* the value words of fix `id` as typed, separated by one space, NUL-terminated: returns the bytes needed (with the NUL), or
+ * -1; with max smaller than that nothing is written */
+long long sf_lammps_ave_chunk_names(void *ptr, const char *id, long long max, char *names);
+/* kernel launches made for chunk/atom computes and fix ave/chunk so far (the sort and the scan of a grouping count as one
+ * each; 0 for a run in which no sample falls and no query or dump names a chunk/atom compute) */
+int sf_lammps_ave_chunk_launches(void *ptr, long long *launches);
+/* measurement (tools/ave_chunk_cost.py): out3 = GPU ms of {assign, sort + segment offsets, sums + fold} of one sample of
+ * fix `id` now, from HIP events; the sums go to a scratch accumulator, the fix's own is untouched */
+int sf_lammps_ave_chunk_cost(void *ptr, const char *id, double *out3);
 /* library.h:61-63 (particle injection / removal; tag[] is double in the reference) */
 int sf_lammps_create_particle(void *ptr, int npAdd, const double *position, const double *tag,
                               double diameter, double rho, int type, const double *vel);

@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/sedifoam_amd.h"
+#include "sf_chunk.h"
 #include "sf_compute_atom.h"
 #include "sf_compute_parse.h"
 #include "sf_dem_dispatch.h"
@@ -278,6 +279,7 @@ void evaluate(SfLammps& L, AtomSet& T, AtomCompute& c)
 
 bool atom_compute_style(const std::string& style)
 {
+  if (style == "chunk/atom") return true;   // (the fifth per-atom style: sf_chunk.hip holds it, the functions below forward)
   for (const char* s : kStyleName)
     if (style == s) return true;
   return false;
@@ -285,6 +287,10 @@ bool atom_compute_style(const std::string& style)
 
 void atom_compute_define(SfLammps& L, const std::vector<std::string>& w)
 {
+  if (w[3] == "chunk/atom") {
+    chunk_compute_define(L, w);
+    return;
+  }
   auto c = std::make_unique<AtomCompute>();
   c->id = w[1];
   c->groupbit = L.eng.group_bit(w[2]);
@@ -303,11 +309,13 @@ int atom_compute_ncols(const SfLammps& L, const std::string& id)
 {
   AtomSet* T = set_of(L);
   const AtomCompute* c = T ? T->find(id) : nullptr;
+  if (!c && chunk_compute_exists(L, id)) return 1;
   return c ? c->ncols() : 0;
 }
 
 void atom_compute_remove(SfLammps& L, const std::string& id)
 {
+  chunk_compute_remove(L, id);
   AtomSet* T = set_of(L);
   if (!T) return;
   for (size_t k = 0; k < T->computes.size(); k++)
@@ -322,6 +330,10 @@ const double* atom_compute_values(SfLammps& L, const std::string& id, int* ncols
 {
   AtomSet* T = set_of(L);
   AtomCompute* c = T ? T->find(id) : nullptr;
+  if (!c && chunk_compute_exists(L, id)) {
+    if (ncols) *ncols = 1;
+    return chunk_compute_values(L, id);
+  }
   if (!c) fail("Could not find compute ID %s", id.c_str());
   const DemEngine& e = L.eng;
   if (c->step != e.nsteps() || c->nbuilds != e.nbuilds() || c->nlocal != e.nlocal()) evaluate(L, *T, *c);
@@ -332,6 +344,7 @@ const double* atom_compute_values(SfLammps& L, const std::string& id, int* ncols
 
 void atom_compute_invalidate(SfLammps& L)
 {
+  chunk_invalidate(L);
   if (AtomSet* T = set_of(L))
     for (auto& c : T->computes) c->step = -1;
 }
@@ -346,6 +359,7 @@ double atom_compute_cost(SfLammps& L, const std::string& id)
 {
   AtomSet* T = set_of(L);
   AtomCompute* c = T ? T->find(id) : nullptr;
+  if (!c && chunk_compute_exists(L, id)) fail("compute %s is a chunk/atom compute: sf_lammps_ave_chunk_cost times its pass", id.c_str());
   if (!c) fail("Could not find compute ID %s", id.c_str());
   hipStream_t st = L.eng.stream();
   hipEvent_t ev[2];

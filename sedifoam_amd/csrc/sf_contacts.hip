@@ -33,6 +33,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/sedifoam_amd.h"
+#include "sf_chunk.h"
 #include "sf_compute_atom.h"
 #include "sf_contacts.h"
 #include "sf_dem_dispatch.h"
@@ -318,6 +319,8 @@ bool compute_command(SfLammps& L, const std::vector<std::string>& w)
     if (!c && !per_atom) fail("Could not find compute ID to delete");   // [3P] Modify::delete_compute
     if (dump_uses_compute(L, w[1]))
       fail("uncompute %s: a dump %s still uses this compute (undump it first)", w[1].c_str(), per_atom ? "custom" : "local");
+    if (ave_chunk_uses_compute(L, w[1]))
+      fail("uncompute %s: a fix ave/chunk still uses this compute (unfix it first)", w[1].c_str());
     if (per_atom) {
       atom_compute_remove(L, w[1]);
       return true;
@@ -334,7 +337,7 @@ bool compute_command(SfLammps& L, const std::vector<std::string>& w)
   const bool per_atom = atom_compute_style(style);
   if (style != "pair/local" && style != "gran/local" && !per_atom)
     fail("Invalid compute style %s (this engine has compute pair/local, also under the name gran/local, and the per-atom "
-         "computes stress/atom, contact/atom, ke/atom and erotate/sphere/atom)", style.c_str());
+         "computes stress/atom, contact/atom, ke/atom, erotate/sphere/atom and chunk/atom)", style.c_str());
   Compute c;
   c.id = w[1];
   c.groupbit = L.eng.group_bit(w[2]);

@@ -41,11 +41,15 @@ struct SfLammps {
   // the per-atom computes and their device buffers (sf_compute_atom.hip); opaque like halo
   void* atom_computes = nullptr;
   void (*atom_computes_delete)(void*) = nullptr;
+  // the chunk/atom computes, the fix ave/chunk commands, their device buffers and files (sf_chunk.hip); opaque like halo
+  void* chunks = nullptr;
+  void (*chunks_delete)(void*) = nullptr;
   ~SfLammps()
   {
     if (restart && restart_delete) restart_delete(restart);
     if (thermo && thermo_delete) thermo_delete(thermo);   // (closes the log and screen files)
     if (dumps && dumps_delete) dumps_delete(dumps);   // (drains the writer: the frames are in their files)
+    if (chunks && chunks_delete) chunks_delete(chunks);   // (closes the files of fix ave/chunk; after the dumps, like computes)
     if (computes && computes_delete) computes_delete(computes);   // (after the dumps, whose frames read its rows)
     if (atom_computes && atom_computes_delete) atom_computes_delete(atom_computes);   // (likewise)
     if (halo && halo_delete) halo_delete(halo);

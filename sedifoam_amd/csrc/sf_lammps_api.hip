@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/sedifoam_amd.h"
+#include "sf_chunk.h"
 #include "sf_compute_atom.h"
 #include "sf_contacts.h"
 #include "sf_dump.h"
@@ -150,15 +151,16 @@ void advance(SfLammps& L, int n)
 // queued batch ends there with the end-of-step state: sub-step s with last = 1, then the dump kernels / the thermo
 // reduction, then the next piece begins with its initial integrate -- what consecutive `run N pre no post no` calls do),
 // and the frame of the current step is written first if it is due ([3P] Output::setup: step 0 at the setup of the first
-// run).  Without a dump and without a thermo destination the run is not cut.
+// run).  A fix ave/chunk cuts the run at its sample steps in the same way (sf_chunk.hip).  Without a dump, a thermo
+// destination, a restart schedule or such a fix the run is not cut.
 void sf::run_steps(SfLammps& L, int n)
 {
-  const bool thermo = sf::thermo_active(L), rst = sf::restart_active(L);
+  const bool thermo = sf::thermo_active(L), rst = sf::restart_active(L), avc = sf::ave_chunk_active(L);
   if (thermo && L.eng.rigid_on() && sf::thermo_needs_dof(L))
     sf::fail("thermo output with temp / press / ke / etotal / p** needs the degrees of freedom of the rigid bodies, which "
              "fix rigid/nve does not keep yet: use thermo_style custom without them, or -screen none -log none");
   sf::restart_run_begin(L);   // (wall rows of a restart file that no fix claimed are dropped here; host only)
-  if (!sf::dump_active(L) && !thermo && !rst) {
+  if (!sf::dump_active(L) && !thermo && !rst && !avc) {
     L.eng.set_thermo_virial(false);
     advance(L, n);
     return;
@@ -166,6 +168,7 @@ void sf::run_steps(SfLammps& L, int n)
   if (thermo) sf::thermo_run_begin(L);   // (the first run: the virial of the setup evaluation)
   advance(L, 0);   // (setup: the frame of the first step holds the forces of the setup evaluation)
   sf::dump_write_due(L);
+  if (avc) sf::ave_chunk_sample_due(L);   // (a sample whose step is this one: fix ave/chunk samples at the setup of a run)
   if (thermo) sf::thermo_setup(L, n);
   const long long end = L.eng.nsteps() + (n > 0 ? n : 0);
   while (L.eng.nsteps() < end) {
@@ -176,8 +179,13 @@ void sf::run_steps(SfLammps& L, int n)
       sf::thermo_arm(L, next);   // (the pair virial of step `next`, when it has a line that shows pressure)
     }
     if (rst) next = std::min(next, sf::restart_next_step(L, L.eng.nsteps()));
+    if (avc) {
+      const long long nx = sf::ave_chunk_next_step(L, L.eng.nsteps());
+      if (nx >= 0) next = std::min(next, nx);
+    }
     advance(L, (int)(next - L.eng.nsteps()));
     sf::dump_write_due(L);
+    if (avc) sf::ave_chunk_sample_due(L);
     if (rst) sf::restart_write_due(L);
     if (thermo) sf::thermo_write_due(L);
   }
@@ -555,8 +563,12 @@ void command(SfLammps& L, const std::string& line)
       sf::fail("velocity: only `velocity GROUP set vx vy vz` is supported");
   } else if (c == "group") {
     cmd_group(L, w);
+  } else if (c == "fix" && w.size() > 3 && w[3] == "ave/chunk") {
+    sf::ave_chunk_fix_command(L, line);   // (from the line: its title keywords may be quoted; sf_chunk.hip)
   } else if (c == "fix") {
     cmd_fix(L, w);
+  } else if (c == "unfix") {
+    sf::unfix_command(L, w);
   } else if (c == "run") {
     if (w.size() < 2) sf::fail("Illegal run command");
     run_steps(L, inum(w[1]));

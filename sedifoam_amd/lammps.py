@@ -192,6 +192,34 @@ class Lammps:
         check(self.L.sf_lammps_compute_atom_cost(self.ptr, str(cid).encode(), C.byref(ms)))
         return ms.value
 
+    def ave_chunk(self, fid):
+        """the latest output of `fix fid group ave/chunk ...`: dict(step, coord[nchunk, ndim] (the centres of the layers),
+        count[nchunk] (Ncount), values[nchunk, nvalues], names (the value words as typed)), chunk 1 first -- what the
+        fix's file holds for that step.  An error before the first output"""
+        fid = str(fid).encode()
+        step = C.c_longlong(); nd = C.c_int(); nv = C.c_int()
+        n = check(self.L.sf_lammps_ave_chunk(self.ptr, fid, 0, C.byref(step), C.byref(nd), C.byref(nv), None, None, None))
+        coord = np.zeros((n, nd.value)); count = np.zeros(n); val = np.zeros((n, nv.value))
+        m = check(self.L.sf_lammps_ave_chunk(self.ptr, fid, n, C.byref(step), C.byref(nd), C.byref(nv), _p(coord), _p(count),
+                                             _p(val)))
+        assert m == n
+        nb = check(self.L.sf_lammps_ave_chunk_names(self.ptr, fid, 0, None))
+        buf = C.create_string_buffer(nb)
+        check(self.L.sf_lammps_ave_chunk_names(self.ptr, fid, nb, buf))
+        return dict(step=step.value, coord=coord, count=count, values=val, names=buf.value.decode().split())
+
+    def ave_chunk_launches(self):
+        """kernel launches made for chunk/atom computes and fix ave/chunk so far"""
+        n = C.c_longlong()
+        check(self.L.sf_lammps_ave_chunk_launches(self.ptr, C.byref(n)))
+        return n.value
+
+    def ave_chunk_cost(self, fid):
+        """GPU ms of (assign, sort + segment offsets, sums + fold) of one sample of fix ave/chunk `fid` now; passive"""
+        out = np.zeros(3)
+        check(self.L.sf_lammps_ave_chunk_cost(self.ptr, str(fid).encode(), _p(out)))
+        return float(out[0]), float(out[1]), float(out[2])
+
     def set_molecule(self, tags, mol):
         """molecule IDs of the atoms with these tags (what `read_data FILE fix ID NULL Molecules` reads from a file)"""
         t, m = _i32(tags), _i32(mol)
