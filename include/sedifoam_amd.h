@@ -173,6 +173,27 @@ int sf_lammps_ave_chunk_launches(void *ptr, long long *launches);
 /* measurement (tools/ave_chunk_cost.py): out3 = GPU ms of {assign, sort + segment offsets, sums + fold} of one sample of
  * fix `id` now, from HIP events; the sums go to a scratch accumulator, the fix's own is untouched */
 int sf_lammps_ave_chunk_cost(void *ptr, const char *id, double *out3);
+/* global computes (the script commands `compute ID group reduce sum|min|max|ave|sumsq|avesq x y z vx vy vz fx fy fz c_ID
+ * c_ID[k] ...`, `compute ID group ke`, `compute ID group erotate/sphere`): the values of compute `id` on the state as it
+ * stands, reduced on the GPU, not normalised.  *is_vector: 1 when the compute is a global vector (c_ID[k]), 0 for a scalar.
+ * Returns the length (1 for a scalar), or -1 (sf_last_error); with max smaller than that (0, to size the array) nothing is
+ * evaluated or written.  Passive: the run goes on with the same bits. */
+long long sf_lammps_compute_global(void *ptr, const char *id, long long max, double *values, int *is_vector);
+/* time series (`fix ID group ave/time Nevery Nrepeat Nfreq c_ID c_ID[k] ... [ave one|running|window M] [start N] [file NAME]
+ * [overwrite] [format STRING] [title1|2 STRING]`, `unfix ID`): the latest output of fix `id`, *step its step and its values
+ * in the order typed -- what the last line of the fix's file holds.  Returns the number of values, or -1 (sf_last_error;
+ * also before the first output: "has made no output yet"); with max smaller than that nothing is written to values. */
+long long sf_lammps_ave_time(void *ptr, const char *id, long long max, long long *step, double *values);
+/* the value words of fix ave/time `id` as typed, separated by one space, NUL-terminated: returns the bytes needed (with the
+ * NUL), or -1; with max smaller than that nothing is written */
+long long sf_lammps_ave_time_names(void *ptr, const char *id, long long max, char *names);
+/* kernel launches made for global computes and fix ave/time so far (0 for a run in which no sample falls, no thermo line
+ * names a compute and no query is made), and *host_copies (may be NULL) the device-to-host copies among them: one per
+ * output of a fix, per compute of a thermo line and per query -- none at a step that is a sample but not an output */
+int sf_lammps_global_launches(void *ptr, long long *launches, long long *host_copies);
+/* measurement (tools/global_cost.py): GPU ms of one fresh evaluation of global compute `id` now, from HIP events (the
+ * per-atom computes behind its c_ inputs are evaluated before the clock starts) */
+int sf_lammps_global_cost(void *ptr, const char *id, double *ms);
 /* library.h:61-63 (particle injection / removal; tag[] is double in the reference) */
 int sf_lammps_create_particle(void *ptr, int npAdd, const double *position, const double *tag,
                               double diameter, double rho, int type, const double *vel);

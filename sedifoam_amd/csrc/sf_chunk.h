@@ -20,7 +20,8 @@ void chunk_invalidate(SfLammps& L);
 // ---- the fix ----
 // `fix ID group ave/chunk ...` from the whole line (its title keywords may be quoted)
 void ave_chunk_fix_command(SfLammps& L, const std::string& line);
-// `unfix ID`
+bool ave_chunk_fix_exists(const SfLammps& L, const std::string& id);
+// `unfix ID`: a fix ave/chunk, or a fix ave/time (sf_global.hip)
 void unfix_command(SfLammps& L, const std::vector<std::string>& w);
 // does a fix ave/chunk name this compute (as its chunk compute or as a c_ value)?
 bool ave_chunk_uses_compute(const SfLammps& L, const std::string& id);

@@ -35,6 +35,7 @@
 #include "sf_chunk_parse.h"
 #include "sf_compute_atom.h"
 #include "sf_contacts.h"
+#include "sf_global.h"
 #include "sf_handles.h"
 
 namespace sf {
@@ -367,7 +368,8 @@ bool per_atom_value(int source) { return source != AS_DENSITY_NUMBER && source !
 void check_compute_value(const SfLammps& L, const AveValue& v)
 {
   const int nc = atom_compute_ncols(L, v.id);
-  if (nc == 0 && pair_local_exists(L, v.id)) fail("Fix ave/chunk compute does not calculate per-atom values");
+  if (nc == 0 && (pair_local_exists(L, v.id) || global_compute_nvalues(L, v.id) > 0))
+    fail("Fix ave/chunk compute does not calculate per-atom values");
   if (nc == 0) fail("Compute ID for fix ave/chunk does not exist");
   if (v.index == 0 && nc != 1) fail("Fix ave/chunk compute does not calculate a per-atom vector");
   if (v.index > 0 && nc == 1) fail("Fix ave/chunk compute does not calculate a per-atom array");
@@ -612,10 +614,12 @@ void ave_chunk_fix_command(SfLammps& L, const std::string& line)
   refuse_decomposed(L, "fix ave/chunk");
   F->groupbit = L.eng.group_bit(F->S.group);
   ChunkSet& T = ensure_set(L);
-  if (T.find_fix(F->S.id)) fail("fix ave/chunk %s: this fix ID is in use (unfix it first)", F->S.id.c_str());
+  if (T.find_fix(F->S.id) || ave_time_fix_exists(L, F->S.id))
+    fail("fix ave/chunk %s: this fix ID is in use (unfix it first)", F->S.id.c_str());
   ChunkCompute* c = T.find(F->S.chunk);
   if (!c) {
-    if (atom_compute_ncols(L, F->S.chunk) > 0 || pair_local_exists(L, F->S.chunk)) fail("Fix ave/chunk does not use chunk/atom compute");
+    if (atom_compute_ncols(L, F->S.chunk) > 0 || pair_local_exists(L, F->S.chunk) || global_compute_nvalues(L, F->S.chunk) > 0)
+      fail("Fix ave/chunk does not use chunk/atom compute");
     fail("Chunk/atom compute does not exist for fix ave/chunk");
   }
   for (const AveValue& v : F->S.values)
@@ -656,8 +660,15 @@ void unfix_command(SfLammps& L, const std::vector<std::string>& w)
         T->fixes.erase(T->fixes.begin() + k);   // (closes its file)
         return;
       }
-  fail("unfix %s: only a fix ave/chunk can be removed, and there is none with this ID (the other fixes stay for the whole "
-       "script)", w[1].c_str());
+  if (ave_time_unfix(L, w[1])) return;
+  fail("unfix %s: only a fix ave/chunk can be removed (or a fix ave/time), and there is none with this ID (the other fixes "
+       "stay for the whole script)", w[1].c_str());
+}
+
+bool ave_chunk_fix_exists(const SfLammps& L, const std::string& id)
+{
+  ChunkSet* T = set_of(L);
+  return T && T->find_fix(id);
 }
 
 bool ave_chunk_uses_compute(const SfLammps& L, const std::string& id)

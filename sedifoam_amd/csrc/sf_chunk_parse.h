@@ -382,10 +382,12 @@ inline std::string parse_ave_chunk(const std::vector<std::string>& w, AveSpec* o
   return std::string();
 }
 
-// the first step >= t0 at which a fix defined at step t0 samples ([3P] FixAveChunk::nextvalid)
-inline long long ave_first_valid(long long t0, long long nevery, long long nrepeat, long long nfreq)
+// the first step >= t0 at which a fix defined at step t0 samples ([3P] FixAveChunk::nextvalid; with `start`, the keyword of
+// fix ave/time, [3P] FixAveTime::nextvalid: no output before step `start`)
+inline long long ave_first_valid(long long t0, long long nevery, long long nrepeat, long long nfreq, long long start = 0)
 {
   long long nv = (t0 / nfreq) * nfreq + nfreq;
+  while (nv < start) nv += nfreq;
   if (nv - nfreq == t0 && nrepeat == 1) nv = t0;
   else nv -= (nrepeat - 1) * nevery;
   if (nv < t0) nv += nfreq;

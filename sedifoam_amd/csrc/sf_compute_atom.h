@@ -1,5 +1,5 @@
-// sf_compute_atom.h -- the per-atom computes `compute ID group stress/atom | contact/atom | ke/atom | erotate/sphere/atom`
-// (sf_compute_atom.hip): one value (stress/atom: six) per owned atom, evaluated on the GPU from the state at the moment of
+// sf_compute_atom.h -- the per-atom computes `compute ID group stress/atom | contact/atom | ke/atom | erotate/sphere/atom |
+// property/atom` (sf_compute_atom.hip): one value (stress/atom: six; property/atom: one per attribute) per owned atom, evaluated on the GPU from the state at the moment of
 // the output, behind the `c_ID` / `c_ID[k]` columns of `dump custom` (sf_dump.hip) and sf_lammps_compute_atom.  They share
 // the ID space of `compute pair/local`: compute_command (sf_contacts.hip) owns `compute` / `uncompute` and hands these
 // styles over.
@@ -14,7 +14,7 @@ struct SfLammps;
 bool atom_compute_style(const std::string& style);
 // `compute ID group STYLE ...` of such a style (the caller has checked that the ID is new)
 void atom_compute_define(SfLammps& L, const std::vector<std::string>& w);
-// columns of compute `id` (1, or 6 for stress/atom); 0: no per-atom compute has this ID
+// columns of compute `id` (1, 6 for stress/atom, the attributes of property/atom); 0: no per-atom compute has this ID
 int atom_compute_ncols(const SfLammps& L, const std::string& id);
 void atom_compute_remove(SfLammps& L, const std::string& id);
 // The values of compute `id` on the state as it stands, field-major on the device: column c of atom index i at

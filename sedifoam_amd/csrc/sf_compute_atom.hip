@@ -9,6 +9,8 @@
 //   compute ID group contact/atom          the partners j (of any group) with rsq < (radi + radj)^2
 //   compute ID group ke/atom               1/2 m v^2
 //   compute ID group erotate/sphere/atom   1/2 (0.4 m r^2) omega^2
+//   compute ID group property/atom a1 ...  id type mass radius diameter x y z vx vy vz fx fy fz omegax omegay omegaz tqx tqy
+//                                          tqz as stored: one attribute a per-atom vector, several an array
 // The group selects the atoms that get a value; atoms outside it read 0.  Like compute pair/local (sf_contacts.hip) a
 // value is evaluated from the state AT THE MOMENT OF THE OUTPUT -- the x v omega a dump custom frame shows, the shear
 // history sf_dem_get_history returns -- with shearupdate = false, and nothing is stored back.  (LAMMPS tallies vatom inside
@@ -26,10 +28,13 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/sedifoam_amd.h"
+#include "sf_atom_terms.h"
 #include "sf_chunk.h"
 #include "sf_compute_atom.h"
 #include "sf_compute_parse.h"
 #include "sf_dem_dispatch.h"
+#include "sf_global.h"
+#include "sf_global_parse.h"
 #include "sf_handles.h"
 
 namespace sf {
@@ -149,17 +154,65 @@ __global__ __launch_bounds__(256) void k_atom_kinetic(const double4* xr, const d
     if (rot) {
       const double4 w = om[i];
       const double r = xr[i].w;
-      e = 0.5 * (0.4 * v.w * r * r) * (w.x * w.x + w.y * w.y + w.z * w.z);
+      e = atom_erotate_term(v, w, r);
     } else
-      e = 0.5 * v.w * (v.x * v.x + v.y * v.y + v.z * v.z);
+      e = atom_ke_term(v);
   }
   val[i] = e;
 }
 
+// the attributes of compute property/atom, as the state records hold them
+struct PropCols {
+  int n;
+  int a[kPropMaxAttrs];
+};
+__global__ __launch_bounds__(256) void k_atom_property(const double4* xr, const double4* vm, const double4* om,
+                                                       const double4* force, const double4* torque, const int* tag,
+                                                       const int* type, const int* mask, int groupbit, PropCols C, int n,
+                                                       double* val)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const bool in = (mask[i] & groupbit) != 0;
+  const double4 zero = make_double4(0.0, 0.0, 0.0, 0.0);
+  const double4 x = in ? xr[i] : zero, v = in ? vm[i] : zero, w = in ? om[i] : zero, f = in ? force[i] : zero,
+                t = in ? torque[i] : zero;
+  const double id = in ? (double)tag[i] : 0.0, ty = in ? (double)type[i] : 0.0;
+#pragma unroll
+  for (int k = 0; k < kPropMaxAttrs; k++) {
+    if (k < C.n) {
+      double o = 0.0;
+      switch (C.a[k]) {
+        case PA_ID: o = id; break;
+        case PA_TYPE: o = ty; break;
+        case PA_MASS: o = v.w; break;
+        case PA_RADIUS: o = x.w; break;
+        case PA_DIAMETER: o = 2.0 * x.w; break;
+        case PA_X: o = x.x; break;
+        case PA_Y: o = x.y; break;
+        case PA_Z: o = x.z; break;
+        case PA_VX: o = v.x; break;
+        case PA_VY: o = v.y; break;
+        case PA_VZ: o = v.z; break;
+        case PA_FX: o = f.x; break;
+        case PA_FY: o = f.y; break;
+        case PA_FZ: o = f.z; break;
+        case PA_OMEGAX: o = w.x; break;
+        case PA_OMEGAY: o = w.y; break;
+        case PA_OMEGAZ: o = w.z; break;
+        case PA_TQX: o = t.x; break;
+        case PA_TQY: o = t.y; break;
+        default: o = t.z; break;
+      }
+      val[(size_t)k * (size_t)n + i] = o;
+    }
+  }
+}
+
 // ---- host side ----
 
-enum Kind { K_STRESS, K_CONTACT, K_KE, K_EROTATE };
-const char* const kStyleName[4] = {"stress/atom", "contact/atom", "ke/atom", "erotate/sphere/atom"};
+enum Kind { K_STRESS, K_CONTACT, K_KE, K_EROTATE, K_PROPERTY };
+const char* const kStyleName[5] = {"stress/atom", "contact/atom", "ke/atom", "erotate/sphere/atom", "property/atom"};
 
 struct Grown {   // device scratch, grown geometrically (no allocation per frame once it has grown)
   void* p = nullptr;
@@ -187,11 +240,12 @@ struct AtomCompute {
   Kind kind = K_KE;
   int groupbit = 1;
   bool ke = true, pair = true;
+  std::vector<int> attrs;   // K_PROPERTY
   Grown val;
   // what the buffer was made at (-1: nothing)
   long long step = -1, nbuilds = -1;
   int nlocal = -1;
-  int ncols() const { return kind == K_STRESS ? 6 : 1; }
+  int ncols() const { return kind == K_STRESS ? 6 : (kind == K_PROPERTY ? (int)attrs.size() : 1); }
 };
 
 struct AtomSet {
@@ -248,6 +302,12 @@ void evaluate(SfLammps& L, AtomSet& T, AtomCompute& c)
     if (c.kind == K_KE || c.kind == K_EROTATE) {
       k_atom_kinetic<<<nb, 256, 0, st>>>(e.d_xr(), e.d_vm(), e.d_om(), e.d_mask(), c.groupbit, c.kind == K_EROTATE ? 1 : 0, n,
                                          val);
+    } else if (c.kind == K_PROPERTY) {
+      PropCols C{};
+      C.n = (int)c.attrs.size();
+      for (int k = 0; k < C.n; k++) C.a[k] = c.attrs[k];
+      k_atom_property<<<nb, 256, 0, st>>>(e.d_xr(), e.d_vm(), e.d_om(), e.d_force(), e.d_torque(), e.d_tag(), e.d_type(),
+                                          e.d_mask(), c.groupbit, C, n, val);
     } else {
       DemPtrs P;
       StepParams S;
@@ -294,10 +354,13 @@ void atom_compute_define(SfLammps& L, const std::vector<std::string>& w)
   auto c = std::make_unique<AtomCompute>();
   c->id = w[1];
   c->groupbit = L.eng.group_bit(w[2]);
-  for (int k = 0; k < 4; k++)
+  for (int k = 0; k < 5; k++)
     if (w[3] == kStyleName[k]) c->kind = (Kind)k;
   if (c->kind == K_STRESS) {
     const std::string err = parse_stress_keywords(w, 4, &c->ke, &c->pair);
+    if (!err.empty()) fail("%s", err.c_str());
+  } else if (c->kind == K_PROPERTY) {
+    const std::string err = parse_property_atom(w, &c->attrs);
     if (!err.empty()) fail("%s", err.c_str());
   } else if (w.size() != 4)
     fail("Illegal compute %s command", w[3].c_str());
@@ -334,6 +397,7 @@ const double* atom_compute_values(SfLammps& L, const std::string& id, int* ncols
     if (ncols) *ncols = 1;
     return chunk_compute_values(L, id);
   }
+  if (!c && global_compute_nvalues(L, id) > 0) fail("compute %s does not calculate per-atom values (it is a global compute)", id.c_str());
   if (!c) fail("Could not find compute ID %s", id.c_str());
   const DemEngine& e = L.eng;
   if (c->step != e.nsteps() || c->nbuilds != e.nbuilds() || c->nlocal != e.nlocal()) evaluate(L, *T, *c);
@@ -345,6 +409,7 @@ const double* atom_compute_values(SfLammps& L, const std::string& id, int* ncols
 void atom_compute_invalidate(SfLammps& L)
 {
   chunk_invalidate(L);
+  global_invalidate(L);
   if (AtomSet* T = set_of(L))
     for (auto& c : T->computes) c->step = -1;
 }

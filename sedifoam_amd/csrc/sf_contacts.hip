@@ -38,7 +38,9 @@
 #include "sf_contacts.h"
 #include "sf_dem_dispatch.h"
 #include "sf_dump_fmt.h"
+#include "sf_global.h"
 #include "sf_handles.h"
+#include "sf_thermo.h"
 
 namespace sf {
 namespace {
@@ -316,7 +318,17 @@ bool compute_command(SfLammps& L, const std::vector<std::string>& w)
     ContactSet* S = set_of(L);
     Compute* c = S ? S->find(w[1]) : nullptr;
     const bool per_atom = !c && atom_compute_ncols(L, w[1]) > 0;   // (one ID space: sf_compute_atom.hip holds the others)
-    if (!c && !per_atom) fail("Could not find compute ID to delete");   // [3P] Modify::delete_compute
+    const bool global = !c && !per_atom && global_compute_nvalues(L, w[1]) > 0;   // (sf_global.hip holds those)
+    if (!c && !per_atom && !global) fail("Could not find compute ID to delete");   // [3P] Modify::delete_compute
+    if (const char* who = global_uses_compute(L, w[1]))
+      fail("uncompute %s: a %s still uses this compute (%s it first)", w[1].c_str(), who,
+           who[0] == 'f' ? "unfix" : "uncompute");
+    if (global) {
+      if (thermo_uses_compute(L, w[1]))
+        fail("uncompute %s: thermo_style custom still names this compute (give another thermo_style first)", w[1].c_str());
+      global_compute_remove(L, w[1]);
+      return true;
+    }
     if (dump_uses_compute(L, w[1]))
       fail("uncompute %s: a dump %s still uses this compute (undump it first)", w[1].c_str(), per_atom ? "custom" : "local");
     if (ave_chunk_uses_compute(L, w[1]))
@@ -334,14 +346,20 @@ bool compute_command(SfLammps& L, const std::vector<std::string>& w)
   if (style == "cohe/local")
     fail("compute cohe/local is not built (fix cohesive is a fix and has no single(); the reference's own code behind it "
          "never terminates)");
-  const bool per_atom = atom_compute_style(style);
-  if (style != "pair/local" && style != "gran/local" && !per_atom)
-    fail("Invalid compute style %s (this engine has compute pair/local, also under the name gran/local, and the per-atom "
-         "computes stress/atom, contact/atom, ke/atom, erotate/sphere/atom and chunk/atom)", style.c_str());
+  const bool per_atom = atom_compute_style(style), global = global_compute_style(style);
+  if (style != "pair/local" && style != "gran/local" && !per_atom && !global)
+    fail("Invalid compute style %s (this engine has compute pair/local, also under the name gran/local, the per-atom "
+         "computes stress/atom, contact/atom, ke/atom, erotate/sphere/atom, property/atom and chunk/atom, and the global "
+         "computes reduce, ke and erotate/sphere)", style.c_str());
   Compute c;
   c.id = w[1];
   c.groupbit = L.eng.group_bit(w[2]);
-  if ((set_of(L) && set_of(L)->find(c.id)) || atom_compute_ncols(L, c.id) > 0) fail("Reuse of compute ID");
+  if ((set_of(L) && set_of(L)->find(c.id)) || atom_compute_ncols(L, c.id) > 0 || global_compute_nvalues(L, c.id) > 0)
+    fail("Reuse of compute ID");
+  if (global) {
+    global_compute_define(L, w);   // (sf_global.hip)
+    return true;
+  }
   if (per_atom) {
     atom_compute_define(L, w);   // (sf_compute_atom.hip)
     return true;
@@ -376,6 +394,8 @@ void compute_lookup(const SfLammps& L, const std::string& id, std::vector<unsign
   const Compute* c = S ? S->find(id) : nullptr;
   if (!c && atom_compute_ncols(L, id) > 0)   // [3P] DumpLocal::parse_fields
     fail("Dump local compute does not compute local info: %s is a per-atom compute (dump custom prints it)", id.c_str());
+  if (!c && global_compute_nvalues(L, id) > 0)
+    fail("Dump local compute does not compute local info: %s is a global compute (fix ave/time and thermo print it)", id.c_str());
   if (!c) fail("Could not find dump local compute ID %s", id.c_str());
   if (values) *values = c->values;
   if (groupbit) *groupbit = c->groupbit;

@@ -1,0 +1,970 @@
+// sf_global.hip -- whole-bed reductions ([3P] LAMMPS names and rules):
+//   compute ID group reduce sum|min|max|ave|sumsq|avesq x y z vx vy vz fx fy fz c_ID c_ID[k] ...
+//       per-atom inputs over the atoms of the group, the columns of a compute pair/local over all of its rows; one input a
+//       global scalar, several a global vector
+//   compute ID group ke | erotate/sphere      the group sums of the terms of ke/atom and erotate/sphere/atom (sf_atom_terms.h)
+//   fix ID group ave/time Nevery Nrepeat Nfreq c_ID c_ID[k] ... [ave one|running|window M] [start N] [file F] [overwrite]
+//       [format S] [title1 S] [title2 S]       time averages of global values, one line per Nfreq steps
+// A value is evaluated from the state AT THE MOMENT OF THE OUTPUT, like a dump frame, and stores nothing back into the run.
+//
+// One evaluation, on the engine's stream:
+//   k_global_gather  a by-value table of up to 16 columns (a component of a state record, a per-atom buffer, a contact-row
+//                    column, a ke / erotate term; a group bit; sum, sum of squares, min or max).  Grid-stride over the
+//                    elements with a grid that depends on the element count alone; a record several columns need is loaded
+//                    once; the accumulators stay in registers; wave64 shuffle tree, then the four waves through LDS
+//                    (sf_block_reduce.h): one partial row per block
+//   k_global_fold    one block folds the partial rows in a fixed order, divides ave / avesq by the count (a count column of
+//                    the same launch, or the row count), stores the values, and adds them into the accumulators of the fix
+//                    ave/time samples due at this step
+// More than 16 columns take more launches; atom columns and row columns have different element counts and go in separate
+// launches.  No floating-point atomics, no scratch: the same state gives the same bits, and which thread adds which element
+// does not depend on the other columns of the launch.  Nothing is copied to the host before an output step, a thermo line
+// or a query.
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <deque>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include <unistd.h>
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/sedifoam_amd.h"
+#include "sf_atom_terms.h"
+#include "sf_block_reduce.h"
+#include "sf_chunk.h"
+#include "sf_compute_atom.h"
+#include "sf_contacts.h"
+#include "sf_global.h"
+#include "sf_global_parse.h"
+#include "sf_handles.h"
+
+// (a*a + s stays a product and a sum, so that a column's bits do not depend on what the compiler fuses around it)
+#pragma clang fp contract(off)
+
+namespace sf {
+namespace {
+
+constexpr int kGCols = 16;          // columns of one launch
+constexpr int kGBlock = 256;
+constexpr int kGMaxBlocks = 1024;   // partial rows
+constexpr int kGAcc = 24;           // accumulator additions one fold launch carries
+constexpr int kPool = 4096;         // device doubles: the values of the computes and the accumulators of the fixes
+
+enum GSrc { GS_XR, GS_VM, GS_OM, GS_FORCE, GS_TORQUE, GS_PTR, GS_INT, GS_ZERO, GS_ONE, GS_KE, GS_EROT };
+enum GOp { GO_SUM, GO_SUMSQ, GO_MIN, GO_MAX };
+enum GNeed { GN_XR = 1, GN_VM = 2, GN_OM = 4, GN_FORCE = 8, GN_TORQUE = 16, GN_MASK = 32 };
+
+struct GCol {
+  const void* p;   // GS_PTR: doubles indexed by element; GS_INT: ints
+  int code;        // src | comp << 8 | op << 16 (comp: x y z w of a record); packed: the table lives in scalar registers
+  int groupbit;    // 0: every element (rows)
+  __host__ __device__ int src() const { return code & 255; }
+  __host__ __device__ int comp() const { return (code >> 8) & 255; }
+  __host__ __device__ int op() const { return code >> 16; }
+  void set(int src, int comp, int op) { code = src | comp << 8 | op << 16; }
+};
+GCol make_col(const void* p, int src, int comp, int groupbit, int op)
+{
+  GCol c;
+  c.p = p;
+  c.groupbit = groupbit;
+  c.set(src, comp, op);
+  return c;
+}
+struct GTable {
+  int n;
+  unsigned need;
+  GCol c[kGCols];
+};
+struct GRecords {
+  const double4 *xr, *vm, *om, *force, *torque;
+  const int* mask;
+};
+struct GFold {
+  int n;
+  int op[kGCols];
+  int div[kGCols];      // -1: none; -2: the row count; >= 0: the count column of this launch
+  double* out[kGCols];  // nullptr: not stored (a count column)
+  int nacc;
+  int acc_col[kGAcc];
+  double* acc_dst[kGAcc];
+};
+struct GAccOnly {   // accumulator additions of values that were already evaluated at this step
+  int n;
+  const double* src[kGAcc];
+  double* dst[kGAcc];
+};
+
+__device__ __forceinline__ double g_identity(int op) { return op == GO_MIN ? 1.0e20 : (op == GO_MAX ? -1.0e20 : 0.0); }
+__device__ __forceinline__ double g_combine(int op, double a, double b)
+{
+  return op == GO_MIN ? fmin(a, b) : (op == GO_MAX ? fmax(a, b) : a + b);
+}
+__device__ __forceinline__ double g_comp(const double4& a, int c) { return c == 0 ? a.x : (c == 1 ? a.y : (c == 2 ? a.z : a.w)); }
+
+__global__ __launch_bounds__(kGBlock) void k_global_gather(GRecords R, GTable T, long long n, double* partial)
+{
+  double acc[kGCols];
+#pragma unroll
+  for (int q = 0; q < kGCols; q++) acc[q] = q < T.n ? g_identity(T.c[q].op()) : 0.0;
+  const long long stride = (long long)gridDim.x * kGBlock;
+  for (long long i = (long long)blockIdx.x * kGBlock + threadIdx.x; i < n; i += stride) {
+    const double4 zero = make_double4(0.0, 0.0, 0.0, 0.0);
+    double4 xr = zero, vm = zero, om = zero, f = zero, tq = zero;
+    int mask = 0;
+    if (T.need & GN_XR) xr = R.xr[i];
+    if (T.need & GN_VM) vm = R.vm[i];
+    if (T.need & GN_OM) om = R.om[i];
+    if (T.need & GN_FORCE) f = R.force[i];
+    if (T.need & GN_TORQUE) tq = R.torque[i];
+    if (T.need & GN_MASK) mask = R.mask[i];
+#pragma unroll
+    for (int q = 0; q < kGCols; q++) {
+      if (q < T.n) {
+        const GCol c = T.c[q];
+        if (c.groupbit == 0 || (mask & c.groupbit)) {
+          double v;
+          switch (c.src()) {
+            case GS_XR: v = g_comp(xr, c.comp()); break;
+            case GS_VM: v = g_comp(vm, c.comp()); break;
+            case GS_OM: v = g_comp(om, c.comp()); break;
+            case GS_FORCE: v = g_comp(f, c.comp()); break;
+            case GS_TORQUE: v = g_comp(tq, c.comp()); break;
+            case GS_PTR: v = static_cast<const double*>(c.p)[i]; break;
+            case GS_INT: v = (double)static_cast<const int*>(c.p)[i]; break;
+            case GS_ONE: v = 1.0; break;
+            case GS_KE: v = atom_ke_term(vm); break;
+            case GS_EROT: v = atom_erotate_term(vm, om, xr.w); break;
+            default: v = 0.0; break;
+          }
+          if (c.op() == GO_SUMSQ) v = v * v;
+          acc[q] = g_combine(c.op(), acc[q], v);
+        }
+      }
+    }
+  }
+  // (c is a compile-time constant in the wave tree and threadIdx.x in the last step: the select keeps the table out of
+  // runtime indexing, which would put it into scratch)
+  auto comb = [&](int c, double a, double b) {
+    int op = GO_SUM;
+#pragma unroll
+    for (int q = 0; q < kGCols; q++)
+      if (q == c) op = T.c[q].op();
+    return g_combine(op, a, b);
+  };
+  block_reduce_store<kGBlock, kGCols>(acc, partial + (size_t)kGCols * blockIdx.x, T.n, comb);
+}
+
+__global__ __launch_bounds__(kGBlock) void k_global_fold(const double* partial, int nb, GFold F, double rowcount)
+{
+  __shared__ double folded[kGCols], fin[kGCols];
+  double v[kGCols];
+#pragma unroll
+  for (int q = 0; q < kGCols; q++) v[q] = q < F.n ? g_identity(F.op[q]) : 0.0;
+  for (int b = threadIdx.x; b < nb; b += kGBlock)
+#pragma unroll
+    for (int q = 0; q < kGCols; q++)
+      if (q < F.n) v[q] = g_combine(F.op[q], v[q], partial[(size_t)kGCols * b + q]);
+  auto comb = [&](int c, double a, double b) {
+    int op = GO_SUM;
+#pragma unroll
+    for (int q = 0; q < kGCols; q++)
+      if (q == c) op = F.op[q];
+    return g_combine(op, a, b);
+  };
+  block_reduce_store<kGBlock, kGCols>(v, folded, F.n, comb);
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < F.n) {
+    int div = -1;
+    double* out = nullptr;
+#pragma unroll
+    for (int q = 0; q < kGCols; q++)
+      if (q == t) {
+        div = F.div[q];
+        out = F.out[q];
+      }
+    double r = folded[t];
+    const double cnt = div == -2 ? rowcount : (div >= 0 ? folded[div] : 0.0);
+    if (cnt > 0.0) r = r / cnt;
+    fin[t] = r;
+    if (out) *out = r;
+  }
+  __syncthreads();
+  if (t < F.nacc) {   // the samples of fix ave/time due at this step: one addition per (fix, value), in sample order
+    int col = 0;
+    double* dst = nullptr;
+#pragma unroll
+    for (int a = 0; a < kGAcc; a++)
+      if (a == t) {
+        col = F.acc_col[a];
+        dst = F.acc_dst[a];
+      }
+    *dst += fin[col];
+  }
+}
+
+__global__ __launch_bounds__(64) void k_global_acc(GAccOnly A)
+{
+  const int t = threadIdx.x;
+  if (t >= A.n) return;
+  const double* src = nullptr;
+  double* dst = nullptr;
+#pragma unroll
+  for (int a = 0; a < kGAcc; a++)
+    if (a == t) {
+      src = A.src[a];
+      dst = A.dst[a];
+    }
+  *dst += *src;
+}
+
+// ---- host side ----
+
+enum GKind { G_REDUCE, G_KE, G_EROTATE };
+const char* const kStyleName[3] = {"reduce", "ke", "erotate/sphere"};
+
+struct GlobalCompute {
+  std::string id;
+  GKind kind = G_REDUCE;
+  int groupbit = 1;
+  ReduceSpec S;
+  int nvalues = 1;
+  int slot = -1;   // in the pool
+  // what the values were made at (-1: nothing)
+  long long step = -1, nbuilds = -1;
+  int nlocal = -1;
+  bool is_vector() const { return kind == G_REDUCE && S.inputs.size() > 1; }
+  bool extensive() const { return kind != G_REDUCE || S.mode == GM_SUM || S.mode == GM_SUMSQ; }
+};
+
+struct AveTimeFix {
+  AveTimeSpec S;
+  long long nvalid = 0;
+  int irepeat = 0;
+  int slot = -1;   // the accumulator, [nvalues] in the pool
+  std::deque<std::vector<double>> blocks;   // ave window: the last M blocks
+  std::vector<double> runsum;               // ave running: the sum of all blocks
+  long long noutputs = 0;
+  bool have = false;
+  long long out_step = -1;
+  std::vector<double> values;
+  FILE* fp = nullptr;
+  long filepos = 0;
+  ~AveTimeFix()
+  {
+    if (fp) fclose(fp);
+  }
+};
+
+struct GlobalSet {
+  std::vector<std::unique_ptr<GlobalCompute>> computes;
+  std::vector<std::unique_ptr<AveTimeFix>> fixes;
+  double* pool = nullptr;
+  std::vector<char> used = std::vector<char>(kPool, 0);
+  double* partial = nullptr;   // [kGMaxBlocks][kGCols]
+  double* h_buf = nullptr;     // pinned [kAveTimeMaxValues]
+  long long launches = 0, host_copies = 0;
+  ~GlobalSet()
+  {
+    if (pool) (void)hipFree(pool);
+    if (partial) (void)hipFree(partial);
+    if (h_buf) (void)hipHostFree(h_buf);
+  }
+  GlobalCompute* find(const std::string& id)
+  {
+    for (auto& c : computes)
+      if (c->id == id) return c.get();
+    return nullptr;
+  }
+  AveTimeFix* find_fix(const std::string& id)
+  {
+    for (auto& f : fixes)
+      if (f->S.id == id) return f.get();
+    return nullptr;
+  }
+  void device(hipStream_t st)
+  {
+    if (pool) return;
+    SF_HIP(hipMalloc(&pool, sizeof(double) * kPool));
+    SF_HIP(hipMemsetAsync(pool, 0, sizeof(double) * kPool, st));
+    SF_HIP(hipMalloc(&partial, sizeof(double) * kGMaxBlocks * kGCols));
+    SF_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_buf), sizeof(double) * kAveTimeMaxValues));
+  }
+  int take(int n)   // n consecutive doubles of the pool, first fit
+  {
+    for (int s = 0; s + n <= kPool; s++) {
+      int k = 0;
+      while (k < n && !used[s + k]) k++;
+      if (k == n) {
+        std::fill(used.begin() + s, used.begin() + s + n, 1);
+        return s;
+      }
+      s += k;
+    }
+    fail("too many global compute values and fix ave/time accumulators (%d doubles in all)", kPool);
+  }
+  void give(int s, int n)
+  {
+    if (s >= 0) std::fill(used.begin() + s, used.begin() + s + n, 0);
+  }
+};
+
+GlobalSet* set_of(const SfLammps& L) { return static_cast<GlobalSet*>(L.globals); }
+GlobalSet& ensure_set(SfLammps& L)
+{
+  if (!L.globals) {
+    L.globals = new GlobalSet();
+    L.globals_delete = [](void* p) { delete static_cast<GlobalSet*>(p); };
+  }
+  return *set_of(L);
+}
+
+void refuse_decomposed(const SfLammps& L, const char* who)
+{
+  const DemEngine& e = L.eng;
+  if (L.world_size > 1 || L.decomposed || e.nranks() > 1 || e.decomposed())
+    fail("%s: one rank only (no decomposed domain)", who);
+}
+
+std::string who_of(const GlobalCompute& c) { return std::string("compute ") + kStyleName[c.kind]; }
+
+bool fresh(const SfLammps& L, const GlobalCompute& c)
+{
+  const DemEngine& e = L.eng;
+  return c.step == e.nsteps() && c.nbuilds == e.nbuilds() && c.nlocal == e.nlocal();
+}
+
+// a c_ input of compute reduce: checked at the compute line and again at every evaluation (the compute may have been
+// removed and defined anew).  Returns true for a compute pair/local, false for a per-atom compute
+bool check_reduce_input(const SfLammps& L, const ReduceInput& in)
+{
+  const int nc = atom_compute_ncols(L, in.id);
+  if (nc > 0) {
+    if (in.index == 0 && nc != 1) fail("Compute reduce compute does not calculate a per-atom vector");
+    if (in.index > 0 && nc == 1) fail("Compute reduce compute does not calculate a per-atom array");
+    if (in.index > nc) fail("Compute reduce compute array is accessed out-of-range");
+    return false;
+  }
+  if (pair_local_exists(L, in.id)) {
+    std::vector<unsigned char> values;
+    compute_lookup(L, in.id, &values, nullptr);
+    const long nv = (long)values.size();
+    if (in.index == 0 && nv != 1) fail("Compute reduce compute does not calculate a local vector");
+    if (in.index > 0 && nv == 1) fail("Compute reduce compute does not calculate a local array");
+    if (in.index > nv) fail("Compute reduce compute array is accessed out-of-range");
+    return true;
+  }
+  if (global_compute_nvalues(L, in.id) > 0)
+    fail("Compute reduce compute calculates global values (c_%s is a global compute: per-atom and local ones are reduced)",
+         in.id.c_str());
+  fail("Compute ID for compute reduce does not exist");
+}
+
+// ---- the plan ----
+
+struct PlanCol {
+  GCol col;
+  bool ave = false;        // divided by the count of its group / of the rows
+  int row_value = 0;       // a row column: which of the values typed on the pair/local line
+  double* out = nullptr;
+  std::vector<double*> acc;
+};
+struct AccReq {   // a sample of a fix: value `value` of compute c is added into *dst
+  const GlobalCompute* c;
+  int value;
+  double* dst;
+};
+
+GOp op_of(int mode)
+{
+  switch (mode) {
+    case GM_MIN: return GO_MIN;
+    case GM_MAX: return GO_MAX;
+    case GM_SUMSQ:
+    case GM_AVESQ: return GO_SUMSQ;
+    default: return GO_SUM;
+  }
+}
+
+unsigned need_of(const GCol& c)
+{
+  unsigned need = c.groupbit ? GN_MASK : 0u;
+  switch (c.src()) {
+    case GS_XR: need |= GN_XR; break;
+    case GS_VM:
+    case GS_KE: need |= GN_VM; break;
+    case GS_OM: need |= GN_OM; break;
+    case GS_FORCE: need |= GN_FORCE; break;
+    case GS_TORQUE: need |= GN_TORQUE; break;
+    case GS_EROT: need |= GN_XR | GN_VM | GN_OM; break;
+    default: break;
+  }
+  return need;
+}
+
+// gather + fold of up to kGCols columns (count columns included) over n elements
+void launch_group(SfLammps& L, GlobalSet& G, const GTable& T, GFold& F, long long n, double rowcount)
+{
+  DemEngine& e = L.eng;
+  hipStream_t st = e.stream();
+  const int nb = n > 0 ? (int)std::min<long long>(kGMaxBlocks, (n + kGBlock - 1) / kGBlock) : 0;
+  if (nb > 0) {
+    GRecords R{e.d_xr(), e.d_vm(), e.d_om(), e.d_force(), e.d_torque(), e.d_mask()};
+    k_global_gather<<<nb, kGBlock, 0, st>>>(R, T, n, G.partial);
+    G.launches++;
+  }
+  k_global_fold<<<1, kGBlock, 0, st>>>(G.partial, nb, F, rowcount);
+  SF_HIP(hipGetLastError());
+  G.launches++;
+}
+
+// the columns `cols` over n elements, in launches of at most kGCols columns; rows: ave divides by the row count
+void launch_columns(SfLammps& L, GlobalSet& G, const std::vector<PlanCol>& cols, long long n, bool rows,
+                    std::vector<std::pair<const double*, double*>>* late_acc)
+{
+  size_t k = 0;
+  while (k < cols.size()) {
+    GTable T{};
+    GFold F{};
+    int count_of[kGCols];   // the group bit a count column counts (0: not a count column)
+    for (int q = 0; q < kGCols; q++) count_of[q] = 0, F.div[q] = -1, F.out[q] = nullptr;
+    while (k < cols.size()) {
+      const PlanCol& pc = cols[k];
+      int cq = -1;
+      if (pc.ave && !rows)
+        for (int q = 0; q < T.n; q++)
+          if (count_of[q] == pc.col.groupbit) cq = q;
+      const int more = 1 + (pc.ave && !rows && cq < 0 ? 1 : 0);
+      if (T.n + more > kGCols) break;
+      if (pc.ave && !rows && cq < 0) {
+        cq = T.n++;
+        T.c[cq] = make_col(nullptr, GS_ONE, 0, pc.col.groupbit, GO_SUM);
+        count_of[cq] = pc.col.groupbit;
+      }
+      const int q = T.n++;
+      T.c[q] = pc.col;
+      F.div[q] = pc.ave ? (rows ? -2 : cq) : -1;
+      F.out[q] = pc.out;
+      for (double* dst : pc.acc) {
+        if (F.nacc < kGAcc) {
+          F.acc_col[F.nacc] = q;
+          F.acc_dst[F.nacc] = dst;
+          F.nacc++;
+        } else
+          late_acc->push_back({pc.out, dst});
+      }
+      k++;
+    }
+    F.n = T.n;
+    for (int q = 0; q < T.n; q++) {
+      F.op[q] = T.c[q].op();
+      T.need |= need_of(T.c[q]);
+    }
+    launch_group(L, G, T, F, n, (double)n);
+  }
+}
+
+void launch_late_acc(SfLammps& L, GlobalSet& G, const std::vector<std::pair<const double*, double*>>& late)
+{
+  for (size_t k = 0; k < late.size(); k += kGAcc) {
+    GAccOnly A{};
+    A.n = (int)std::min<size_t>(kGAcc, late.size() - k);
+    for (int a = 0; a < A.n; a++) {
+      A.src[a] = late[k + a].first;
+      A.dst[a] = late[k + a].second;
+    }
+    k_global_acc<<<1, 64, 0, L.eng.stream()>>>(A);
+    SF_HIP(hipGetLastError());
+    G.launches++;
+  }
+}
+
+// Every compute of `want` that is stale is evaluated, once; `accs`: the additions of the fix samples due now, carried by
+// the fold launches of the values they name (or by k_global_acc where the value was evaluated at this step before)
+void evaluate(SfLammps& L, GlobalSet& G, const std::vector<GlobalCompute*>& want, const std::vector<AccReq>& accs)
+{
+  DemEngine& e = L.eng;
+  hipStream_t st = e.stream();
+  G.device(st);
+  const int n = e.nlocal();
+  std::vector<PlanCol> atom_cols;
+  std::vector<std::pair<std::string, std::vector<PlanCol>>> row_cols;   // per compute pair/local
+  std::vector<std::pair<const double*, double*>> late;
+  std::vector<GlobalCompute*> stale;
+  for (GlobalCompute* c : want) {
+    refuse_decomposed(L, who_of(*c).c_str());
+    if (std::find(stale.begin(), stale.end(), c) != stale.end()) continue;
+    if (fresh(L, *c)) continue;
+    stale.push_back(c);
+  }
+  for (const AccReq& a : accs)
+    if (std::find(stale.begin(), stale.end(), a.c) == stale.end()) late.push_back({G.pool + a.c->slot + a.value, a.dst});
+  for (GlobalCompute* c : stale) {
+    for (int j = 0; j < c->nvalues; j++) {
+      PlanCol pc;
+      pc.out = G.pool + c->slot + j;
+      for (const AccReq& a : accs)
+        if (a.c == c && a.value == j) pc.acc.push_back(a.dst);
+      pc.col = make_col(nullptr, GS_ZERO, 0, c->groupbit, GO_SUM);
+      if (c->kind == G_KE) pc.col.set(GS_KE, 0, GO_SUM);
+      else if (c->kind == G_EROTATE) pc.col.set(GS_EROT, 0, GO_SUM);
+      else {
+        const ReduceInput& in = c->S.inputs[j];
+        const GOp op = op_of(c->S.mode);
+        pc.ave = c->S.mode == GM_AVE || c->S.mode == GM_AVESQ;
+        if (in.attr != GA_COMPUTE) {
+          pc.col.set(in.attr < GA_VX ? GS_XR : (in.attr < GA_FX ? GS_VM : GS_FORCE), in.attr % 3, op);
+        } else if (!check_reduce_input(L, in)) {
+          int nc = 0;
+          const double* val = atom_compute_values(L, in.id, &nc);   // (once per step however many ask)
+          pc.col.set(GS_PTR, 0, op);
+          pc.col.p = val ? val + (size_t)(in.index > 0 ? in.index - 1 : 0) * (size_t)n : nullptr;
+        } else {
+          pc.col.groupbit = 0;   // every row, whatever the group of the reduce
+          pc.col.set(GS_ZERO, 0, op);
+          pc.row_value = (int)(in.index > 0 ? in.index - 1 : 0);   // (the source is filled in once the rows exist)
+          size_t r = 0;
+          while (r < row_cols.size() && row_cols[r].first != in.id) r++;
+          if (r == row_cols.size()) row_cols.push_back({in.id, {}});
+          row_cols[r].second.push_back(pc);
+          continue;
+        }
+      }
+      atom_cols.push_back(pc);
+    }
+  }
+  launch_columns(L, G, atom_cols, n, false, &late);
+  for (auto& rc : row_cols) {
+    std::vector<unsigned char> values;
+    int groupbit = 1;
+    compute_lookup(L, rc.first, &values, &groupbit);
+    const ContactRows R = contact_rows(L, groupbit);   // (reads the row count on the host: one wait)
+    for (PlanCol& pc : rc.second) {
+      const int v = values[pc.row_value];
+      const int op = pc.col.op();
+      if (v < kContactDoubles) {
+        pc.col.set(GS_PTR, 0, op);
+        pc.col.p = R.val ? R.val + (size_t)v * (size_t)R.n : nullptr;
+      } else if (v == CV_TAG1 || v == CV_TAG2) {
+        pc.col.set(GS_INT, 0, op);
+        pc.col.p = v == CV_TAG1 ? R.tag1 : R.tag2;
+      } else
+        pc.col.set(GS_ZERO, 0, op);   // eng
+    }
+    launch_columns(L, G, rc.second, R.n, true, &late);   // (before the next compute's rows take the same buffers)
+  }
+  launch_late_acc(L, G, late);
+  for (GlobalCompute* c : stale) {
+    c->step = e.nsteps();
+    c->nbuilds = e.nbuilds();
+    c->nlocal = n;
+  }
+}
+
+void copy_to_host(SfLammps& L, GlobalSet& G, int slot, int n, bool zero_after)
+{
+  hipStream_t st = L.eng.stream();
+  SF_HIP(hipMemcpyAsync(G.h_buf, G.pool + slot, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+  if (zero_after) SF_HIP(hipMemsetAsync(G.pool + slot, 0, sizeof(double) * (size_t)n, st));
+  SF_HIP(hipStreamSynchronize(st));
+  G.host_copies++;
+}
+
+// ---- fix ave/time ----
+
+// checked at the fix line and again at every sample (the compute may have been redefined)
+void check_fix_value(const SfLammps& L, const AveTimeValue& v)
+{
+  bool vec = false;
+  const int n = global_compute_nvalues(L, v.id, &vec);
+  if (n == 0) {
+    if (atom_compute_ncols(L, v.id) > 0 || pair_local_exists(L, v.id))
+      fail(v.index == 0 ? "Fix ave/time compute does not calculate a scalar" : "Fix ave/time compute does not calculate a vector");
+    fail("Compute ID for fix ave/time does not exist");
+  }
+  if (v.index == 0 && vec) fail("Fix ave/time compute does not calculate a scalar");
+  if (v.index > 0 && !vec) fail("Fix ave/time compute does not calculate a vector");
+  if (v.index > n) fail("Fix ave/time compute vector is accessed out-of-range");
+}
+
+void write_line(AveTimeFix& F)
+{
+  if (!F.fp) return;
+  if (F.S.overwrite && fseek(F.fp, F.filepos, SEEK_SET) != 0) fail("fix ave/time %s: cannot rewind %s", F.S.id.c_str(), F.S.file.c_str());
+  fprintf(F.fp, "%lld", F.out_step);
+  for (double v : F.values) fprintf(F.fp, F.S.format.c_str(), v);
+  fputc('\n', F.fp);
+  if (fflush(F.fp) != 0) fail("fix ave/time %s: error writing %s", F.S.id.c_str(), F.S.file.c_str());
+  if (F.S.overwrite) {
+    const long end = ftell(F.fp);
+    if (end < 0 || ftruncate(fileno(F.fp), end) != 0) fail("fix ave/time %s: cannot truncate %s", F.S.id.c_str(), F.S.file.c_str());
+  }
+}
+
+// the accumulator of Nrepeat samples -> one output (divided on the host)
+void make_output(SfLammps& L, GlobalSet& G, AveTimeFix& F)
+{
+  const int nv = (int)F.S.values.size();
+  copy_to_host(L, G, F.slot, nv, true);
+  std::vector<double> block(nv);
+  const double nrep = (double)F.S.nrepeat;
+  for (int j = 0; j < nv; j++) block[j] = G.h_buf[j] / nrep;
+  F.noutputs++;
+  F.values.assign(nv, 0.0);
+  if (F.S.ave == AT_ONE) F.values = block;
+  else if (F.S.ave == AT_RUNNING) {
+    if (F.runsum.empty()) F.runsum.assign(nv, 0.0);
+    for (int j = 0; j < nv; j++) {
+      F.runsum[j] += block[j];
+      F.values[j] = F.runsum[j] / (double)F.noutputs;
+    }
+  } else {
+    F.blocks.push_back(block);
+    if ((long)F.blocks.size() > F.S.window) F.blocks.pop_front();
+    for (int j = 0; j < nv; j++) {
+      double s = 0.0;
+      for (const auto& b : F.blocks) s += b[j];   // (oldest first)
+      F.values[j] = s / (double)F.blocks.size();
+    }
+  }
+  F.out_step = L.eng.nsteps();
+  F.have = true;
+  write_line(F);
+}
+
+long long first_valid(const AveTimeFix& F, long long t0) { return ave_first_valid(t0, F.S.nevery, F.S.nrepeat, F.S.nfreq, F.S.start); }
+
+// a fix whose sample step has passed without a sample (steps taken outside run_steps): begin a new output
+void catch_up(SfLammps& L, GlobalSet& G, AveTimeFix& F)
+{
+  const long long step = L.eng.nsteps();
+  if (F.nvalid >= step) return;
+  F.nvalid = first_valid(F, step);
+  if (F.irepeat > 0) {
+    F.irepeat = 0;
+    SF_HIP(hipMemsetAsync(G.pool + F.slot, 0, sizeof(double) * F.S.values.size(), L.eng.stream()));
+  }
+}
+
+GlobalCompute& compute_of(GlobalSet& G, const std::string& id, const char* missing)
+{
+  GlobalCompute* c = G.find(id);
+  if (!c) fail("%s", missing);
+  return *c;
+}
+
+}  // namespace
+
+// ---- the computes ----
+
+bool global_compute_style(const std::string& style)
+{
+  if (style == "reduce/region") return true;   // (refused by name in global_compute_define)
+  for (const char* s : kStyleName)
+    if (style == s) return true;
+  return false;
+}
+
+void global_compute_define(SfLammps& L, const std::vector<std::string>& w)
+{
+  if (w[3] == "reduce/region") fail("compute reduce/region is not supported (there is no region command): compute reduce is");
+  auto c = std::make_unique<GlobalCompute>();
+  c->id = w[1];
+  c->groupbit = L.eng.group_bit(w[2]);
+  for (int k = 0; k < 3; k++)
+    if (w[3] == kStyleName[k]) c->kind = (GKind)k;
+  refuse_decomposed(L, who_of(*c).c_str());
+  if (c->kind == G_REDUCE) {
+    const std::string err = parse_reduce(w, &c->S);
+    if (!err.empty()) fail("%s", err.c_str());
+    for (const ReduceInput& in : c->S.inputs)
+      if (in.attr == GA_COMPUTE) check_reduce_input(L, in);
+    c->nvalues = (int)c->S.inputs.size();
+  } else if (w.size() != 4)
+    fail("Illegal compute %s command", w[3].c_str());
+  GlobalSet& G = ensure_set(L);
+  c->slot = G.take(c->nvalues);
+  G.computes.push_back(std::move(c));
+}
+
+int global_compute_nvalues(const SfLammps& L, const std::string& id, bool* is_vector, bool* extensive)
+{
+  GlobalSet* G = set_of(L);
+  const GlobalCompute* c = G ? G->find(id) : nullptr;
+  if (!c) return 0;
+  if (is_vector) *is_vector = c->is_vector();
+  if (extensive) *extensive = c->extensive();
+  return c->nvalues;
+}
+
+void global_compute_remove(SfLammps& L, const std::string& id)
+{
+  GlobalSet* G = set_of(L);
+  if (!G) return;
+  for (size_t k = 0; k < G->computes.size(); k++)
+    if (G->computes[k]->id == id) {
+      SF_HIP(hipStreamSynchronize(L.eng.stream()));   // (a launch queued on the stream may still write its values)
+      G->give(G->computes[k]->slot, G->computes[k]->nvalues);
+      G->computes.erase(G->computes.begin() + k);
+      return;
+    }
+}
+
+const char* global_uses_compute(const SfLammps& L, const std::string& id)
+{
+  const GlobalSet* G = set_of(L);
+  if (!G) return nullptr;
+  for (const auto& c : G->computes)
+    if (c->kind == G_REDUCE)
+      for (const ReduceInput& in : c->S.inputs)
+        if (in.attr == GA_COMPUTE && in.id == id) return "compute reduce";
+  for (const auto& f : G->fixes)
+    for (const AveTimeValue& v : f->S.values)
+      if (v.id == id) return "fix ave/time";
+  return nullptr;
+}
+
+void global_invalidate(SfLammps& L)
+{
+  if (GlobalSet* G = set_of(L))
+    for (auto& c : G->computes) c->step = -1;
+}
+
+void global_values_host(SfLammps& L, const std::string& id, std::vector<double>* out)
+{
+  GlobalSet* G = set_of(L);
+  GlobalCompute* c = G ? G->find(id) : nullptr;
+  if (!c) fail("Could not find compute ID %s", id.c_str());
+  evaluate(L, *G, {c}, {});
+  copy_to_host(L, *G, c->slot, c->nvalues, false);
+  out->assign(G->h_buf, G->h_buf + c->nvalues);
+}
+
+// ---- the fix ----
+
+void ave_time_fix_command(SfLammps& L, const std::string& line)
+{
+  std::vector<std::string> w;
+  const std::string qerr = split_quoted(line, &w);
+  if (!qerr.empty()) fail("%s", qerr.c_str());
+  auto F = std::make_unique<AveTimeFix>();
+  const std::string err = parse_ave_time(w, &F->S);
+  if (!err.empty()) fail("%s", err.c_str());
+  refuse_decomposed(L, "fix ave/time");
+  (void)L.eng.group_bit(F->S.group);   // (the group must exist; it is not used, as in LAMMPS)
+  GlobalSet& G = ensure_set(L);
+  if (G.find_fix(F->S.id) || ave_chunk_fix_exists(L, F->S.id))
+    fail("fix ave/time %s: this fix ID is in use (unfix it first)", F->S.id.c_str());
+  for (const AveTimeValue& v : F->S.values) check_fix_value(L, v);
+  hipStream_t st = L.eng.stream();
+  G.device(st);
+  const int nv = (int)F->S.values.size();
+  F->nvalid = first_valid(*F, L.eng.nsteps());
+  if (!F->S.file.empty()) {
+    F->fp = fopen(F->S.file.c_str(), "w+");
+    if (!F->fp) fail("Cannot open fix ave/time file %s", F->S.file.c_str());
+    std::string t2 = "# TimeStep";
+    for (const AveTimeValue& v : F->S.values) t2 += " " + v.word;
+    const std::string t1 = "# Time-averaged data for fix " + F->S.id;
+    fprintf(F->fp, "%s\n%s\n", (F->S.has_title[0] ? F->S.title[0] : t1).c_str(), (F->S.has_title[1] ? F->S.title[1] : t2).c_str());
+    fflush(F->fp);
+    F->filepos = ftell(F->fp);
+  }
+  F->slot = G.take(nv);
+  SF_HIP(hipMemsetAsync(G.pool + F->slot, 0, sizeof(double) * (size_t)nv, st));
+  G.fixes.push_back(std::move(F));
+}
+
+bool ave_time_fix_exists(const SfLammps& L, const std::string& id)
+{
+  GlobalSet* G = set_of(L);
+  return G && G->find_fix(id);
+}
+
+bool ave_time_unfix(SfLammps& L, const std::string& id)
+{
+  GlobalSet* G = set_of(L);
+  if (!G) return false;
+  for (size_t k = 0; k < G->fixes.size(); k++)
+    if (G->fixes[k]->S.id == id) {
+      SF_HIP(hipStreamSynchronize(L.eng.stream()));   // (a sample queued on the stream may still add into its accumulator)
+      G->give(G->fixes[k]->slot, (int)G->fixes[k]->S.values.size());
+      G->fixes.erase(G->fixes.begin() + k);   // (closes its file)
+      return true;
+    }
+  return false;
+}
+
+bool ave_time_active(const SfLammps& L)
+{
+  const GlobalSet* G = set_of(L);
+  return G && !G->fixes.empty();
+}
+
+long long ave_time_next_step(const SfLammps& L, long long step)
+{
+  const GlobalSet* G = set_of(L);
+  long long best = -1;
+  if (!G) return best;
+  for (const auto& f : G->fixes) {
+    const long long nx = f->nvalid > step ? f->nvalid : first_valid(*f, step + 1);
+    if (best < 0 || nx < best) best = nx;
+  }
+  return best;
+}
+
+void global_step_due(SfLammps& L, const std::vector<std::string>& also)
+{
+  GlobalSet* G = set_of(L);
+  if (!G) return;
+  const long long step = L.eng.nsteps();
+  std::vector<AveTimeFix*> due;
+  for (auto& f : G->fixes) {
+    catch_up(L, *G, *f);
+    if (f->nvalid == step) due.push_back(f.get());
+  }
+  if (due.empty() && also.empty()) return;
+  if (!due.empty()) refuse_decomposed(L, "fix ave/time");
+  std::vector<GlobalCompute*> want;
+  std::vector<AccReq> accs;
+  for (AveTimeFix* f : due)
+    for (size_t j = 0; j < f->S.values.size(); j++) {
+      const AveTimeValue& v = f->S.values[j];
+      check_fix_value(L, v);
+      GlobalCompute& c = compute_of(*G, v.id, "Compute ID for fix ave/time does not exist");
+      want.push_back(&c);
+      accs.push_back({&c, (int)(v.index > 0 ? v.index - 1 : 0), G->pool ? G->pool + f->slot + j : nullptr});
+    }
+  for (const std::string& id : also) want.push_back(&compute_of(*G, id, "Could not find thermo custom compute ID"));
+  evaluate(L, *G, want, accs);
+  for (AveTimeFix* f : due) {
+    f->irepeat++;
+    if (f->irepeat < f->S.nrepeat) {
+      f->nvalid = step + f->S.nevery;
+      continue;
+    }
+    f->irepeat = 0;
+    f->nvalid = step + f->S.nfreq - (f->S.nrepeat - 1) * f->S.nevery;
+    make_output(L, *G, *f);
+  }
+}
+
+}  // namespace sf
+
+namespace {
+sf::SfLammps* handle(void* p)
+{
+  if (!p) sf::fail("null engine handle");
+  return static_cast<sf::SfLammps*>(p);
+}
+}  // namespace
+
+extern "C" {
+
+long long sf_lammps_compute_global(void* ptr, const char* id, long long max, double* values, int* is_vector)
+{
+  long long n = 0;
+  SF_API_BEGIN
+  sf::SfLammps& L = *handle(ptr);
+  if (!id) sf::fail("sf_lammps_compute_global: null argument");
+  bool vec = false;
+  n = sf::global_compute_nvalues(L, id, &vec);
+  if (n == 0) {
+    if (sf::atom_compute_ncols(L, id) > 0 || sf::pair_local_exists(L, id))
+      sf::fail("compute %s does not calculate a global scalar or vector (sf_lammps_compute_atom and sf_lammps_get_contacts "
+               "return per-atom and local values)", id);
+    sf::fail("Could not find compute ID %s", id);
+  }
+  if (is_vector) *is_vector = vec ? 1 : 0;
+  if (n <= max) {
+    if (!values) sf::fail("sf_lammps_compute_global: null argument");
+    std::vector<double> v;
+    sf::global_values_host(L, id, &v);
+    std::copy(v.begin(), v.end(), values);
+  }
+  SF_API_END(n)
+}
+
+long long sf_lammps_ave_time(void* ptr, const char* id, long long max, long long* step, double* values)
+{
+  long long n = 0;
+  SF_API_BEGIN
+  if (!id) sf::fail("sf_lammps_ave_time: null argument");
+  sf::GlobalSet* G = sf::set_of(*handle(ptr));
+  sf::AveTimeFix* F = G ? G->find_fix(id) : nullptr;
+  if (!F) sf::fail("Could not find fix ave/time ID %s", id);
+  if (!F->have) sf::fail("fix ave/time %s has made no output yet (the first one is due at a multiple of Nfreq)", id);
+  if (step) *step = F->out_step;
+  n = (long long)F->values.size();
+  if (n <= max) {
+    if (!values) sf::fail("sf_lammps_ave_time: null argument");
+    std::copy(F->values.begin(), F->values.end(), values);
+  }
+  SF_API_END(n)
+}
+
+long long sf_lammps_ave_time_names(void* ptr, const char* id, long long max, char* names)
+{
+  long long n = 0;
+  SF_API_BEGIN
+  if (!id) sf::fail("sf_lammps_ave_time_names: null argument");
+  sf::GlobalSet* G = sf::set_of(*handle(ptr));
+  sf::AveTimeFix* F = G ? G->find_fix(id) : nullptr;
+  if (!F) sf::fail("Could not find fix ave/time ID %s", id);
+  std::string s;
+  for (const sf::AveTimeValue& v : F->S.values) s += (s.empty() ? "" : " ") + v.word;
+  n = (long long)s.size() + 1;
+  if (n <= max) {
+    if (!names) sf::fail("sf_lammps_ave_time_names: null argument");
+    std::memcpy(names, s.c_str(), (size_t)n);
+  }
+  SF_API_END(n)
+}
+
+int sf_lammps_global_launches(void* ptr, long long* launches, long long* host_copies)
+{
+  SF_API_BEGIN
+  if (!launches) sf::fail("sf_lammps_global_launches: null argument");
+  const sf::GlobalSet* G = sf::set_of(*handle(ptr));
+  *launches = G ? G->launches : 0;
+  if (host_copies) *host_copies = G ? G->host_copies : 0;
+  SF_API_END(0)
+}
+
+int sf_lammps_global_cost(void* ptr, const char* id, double* ms)
+{
+  SF_API_BEGIN
+  sf::SfLammps& L = *handle(ptr);
+  if (!id || !ms) sf::fail("sf_lammps_global_cost: null argument");
+  sf::GlobalSet* G = sf::set_of(L);
+  sf::GlobalCompute* c = G ? G->find(id) : nullptr;
+  if (!c) sf::fail("Could not find compute ID %s", id);
+  hipStream_t st = L.eng.stream();
+  hipEvent_t ev[2];
+  for (hipEvent_t& e : ev) SF_HIP(hipEventCreate(&e));
+  struct EvGuard {
+    hipEvent_t* ev;
+    ~EvGuard()
+    {
+      for (int k = 0; k < 2; k++) (void)hipEventDestroy(ev[k]);
+    }
+  } guard{ev};
+  // (the per-atom computes behind c_ inputs are evaluated outside the time: sf_lammps_compute_atom_cost times them)
+  sf::evaluate(L, *G, {c}, {});
+  c->step = -1;
+  SF_HIP(hipEventRecord(ev[0], st));
+  sf::evaluate(L, *G, {c}, {});
+  SF_HIP(hipEventRecord(ev[1], st));
+  SF_HIP(hipStreamSynchronize(st));
+  float t = 0.f;
+  SF_HIP(hipEventElapsedTime(&t, ev[0], ev[1]));
+  *ms = (double)t;
+  SF_API_END(0)
+}
+
+}  // extern "C"

@@ -44,11 +44,15 @@ struct SfLammps {
   // the chunk/atom computes, the fix ave/chunk commands, their device buffers and files (sf_chunk.hip); opaque like halo
   void* chunks = nullptr;
   void (*chunks_delete)(void*) = nullptr;
+  // the global computes, the fix ave/time commands, their device values, accumulators and files (sf_global.hip); opaque like halo
+  void* globals = nullptr;
+  void (*globals_delete)(void*) = nullptr;
   ~SfLammps()
   {
     if (restart && restart_delete) restart_delete(restart);
     if (thermo && thermo_delete) thermo_delete(thermo);   // (closes the log and screen files)
     if (dumps && dumps_delete) dumps_delete(dumps);   // (drains the writer: the frames are in their files)
+    if (globals && globals_delete) globals_delete(globals);   // (closes the files of fix ave/time)
     if (chunks && chunks_delete) chunks_delete(chunks);   // (closes the files of fix ave/chunk; after the dumps, like computes)
     if (computes && computes_delete) computes_delete(computes);   // (after the dumps, whose frames read its rows)
     if (atom_computes && atom_computes_delete) atom_computes_delete(atom_computes);   // (likewise)

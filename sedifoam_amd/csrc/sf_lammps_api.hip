@@ -20,6 +20,7 @@
 #include "sf_contacts.h"
 #include "sf_dump.h"
 #include "sf_env.h"
+#include "sf_global.h"
 #include "sf_handles.h"
 #include "sf_restart.h"
 #include "sf_rigid.h"
@@ -156,11 +157,12 @@ void advance(SfLammps& L, int n)
 void sf::run_steps(SfLammps& L, int n)
 {
   const bool thermo = sf::thermo_active(L), rst = sf::restart_active(L), avc = sf::ave_chunk_active(L);
+  const bool avt = sf::ave_time_active(L);
   if (thermo && L.eng.rigid_on() && sf::thermo_needs_dof(L))
     sf::fail("thermo output with temp / press / ke / etotal / p** needs the degrees of freedom of the rigid bodies, which "
              "fix rigid/nve does not keep yet: use thermo_style custom without them, or -screen none -log none");
   sf::restart_run_begin(L);   // (wall rows of a restart file that no fix claimed are dropped here; host only)
-  if (!sf::dump_active(L) && !thermo && !rst && !avc) {
+  if (!sf::dump_active(L) && !thermo && !rst && !avc && !avt) {
     L.eng.set_thermo_virial(false);
     advance(L, n);
     return;
@@ -169,6 +171,8 @@ void sf::run_steps(SfLammps& L, int n)
   advance(L, 0);   // (setup: the frame of the first step holds the forces of the setup evaluation)
   sf::dump_write_due(L);
   if (avc) sf::ave_chunk_sample_due(L);   // (a sample whose step is this one: fix ave/chunk samples at the setup of a run)
+  // the global computes of this step, one plan: the fix ave/time samples due and the c_ columns of the thermo line
+  if (avt || thermo) sf::global_step_due(L, sf::thermo_global_ids_due(L, true, n));
   if (thermo) sf::thermo_setup(L, n);
   const long long end = L.eng.nsteps() + (n > 0 ? n : 0);
   while (L.eng.nsteps() < end) {
@@ -183,9 +187,14 @@ void sf::run_steps(SfLammps& L, int n)
       const long long nx = sf::ave_chunk_next_step(L, L.eng.nsteps());
       if (nx >= 0) next = std::min(next, nx);
     }
+    if (avt) {
+      const long long nx = sf::ave_time_next_step(L, L.eng.nsteps());
+      if (nx >= 0) next = std::min(next, nx);
+    }
     advance(L, (int)(next - L.eng.nsteps()));
     sf::dump_write_due(L);
     if (avc) sf::ave_chunk_sample_due(L);
+    if (avt || thermo) sf::global_step_due(L, sf::thermo_global_ids_due(L, false, 0));
     if (rst) sf::restart_write_due(L);
     if (thermo) sf::thermo_write_due(L);
   }
@@ -563,6 +572,8 @@ void command(SfLammps& L, const std::string& line)
       sf::fail("velocity: only `velocity GROUP set vx vy vz` is supported");
   } else if (c == "group") {
     cmd_group(L, w);
+  } else if (c == "fix" && w.size() > 3 && w[3] == "ave/time") {
+    sf::ave_time_fix_command(L, line);   // (from the line: its titles and format may be quoted; sf_global.hip)
   } else if (c == "fix" && w.size() > 3 && w[3] == "ave/chunk") {
     sf::ave_chunk_fix_command(L, line);   // (from the line: its title keywords may be quoted; sf_chunk.hip)
   } else if (c == "fix") {

@@ -44,6 +44,12 @@ void thermo_run_end(SfLammps& L);
 
 // the value of `keyword` in the last line written: 0, -1 when no line was written yet, -2 for an unknown keyword
 int thermo_get(const SfLammps& L, const std::string& keyword, double* out);
+// the global computes the c_ID / c_ID[k] columns of the current style name (sf_global.hip evaluates them): those of the
+// line due at the engine's current step -- at the setup of a run (`setup`), at a multiple of N or at the run's last step --
+// or nothing when no line is due or no destination is open
+std::vector<std::string> thermo_global_ids_due(const SfLammps& L, bool setup, int run_n);
+// does the current thermo style name compute `id`?
+bool thermo_uses_compute(const SfLammps& L, const std::string& id);
 // kernel launches made for thermo output so far (the virial pass and the reductions)
 long long thermo_launches(const SfLammps& L);
 

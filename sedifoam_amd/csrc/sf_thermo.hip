@@ -26,8 +26,13 @@
 #include <vector>
 
 #include "../../include/sedifoam_amd.h"
+#include "sf_block_reduce.h"
+#include "sf_compute_atom.h"
+#include "sf_contacts.h"
 #include "sf_dem_dispatch.h"
 #include "sf_env.h"
+#include "sf_global.h"
+#include "sf_global_parse.h"
 #include "sf_handles.h"
 #include "sf_thermo.h"
 
@@ -43,29 +48,12 @@ constexpr int kResult = 14;   // the final pass: kinetic tensor (6), f.f, virial
 
 __device__ __forceinline__ Vec3 tv3(const double4& a) { return {a.x, a.y, a.z}; }
 
-// NV values per thread -> one row per block at out: wave shuffle tree, then the waves' partials in wave order.  The first
-// NV - NMAX components are sums, the last NMAX maxima.  Fixed order throughout.
+// NV values per thread -> one row per block at out (sf_block_reduce.h): the first NV - NMAX components are sums, the last
+// NMAX maxima.  Fixed order throughout.
 template <int NV, int NMAX>
 __device__ __forceinline__ void block_reduce_store(double (&v)[NV], double* out)
 {
-  __shared__ double ws[kThermoBlock / 64][NV];
-  for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-    for (int c = 0; c < NV; c++) {
-      const double o = __shfl_down(v[c], off, 64);
-      v[c] = c < NV - NMAX ? v[c] + o : fmax(v[c], o);
-    }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0)
-#pragma unroll
-    for (int c = 0; c < NV; c++) ws[w][c] = v[c];
-  __syncthreads();
-  if ((int)threadIdx.x < NV) {
-    const int c = threadIdx.x;
-    double t = ws[0][c];
-    for (int k = 1; k < kThermoBlock / 64; k++) t = c < NV - NMAX ? t + ws[k][c] : fmax(t, ws[k][c]);
-    out[c] = t;
-  }
+  sf::block_reduce_store<kThermoBlock, NV>(v, out, NV, [](int c, double a, double b) { return c < NV - NMAX ? a + b : fmax(a, b); });
 }
 
 // The pair virial of one force evaluation: the neighbour loop of substep_particle (sf_dem_kernels.h) without its
@@ -214,10 +202,17 @@ const KeyInfo kKeys[K_COUNT] = {
 };
 const std::vector<int> kStyleOne = {K_STEP, K_TEMP, K_EPAIR, K_EMOL, K_ETOTAL, K_PRESS};
 
+struct ComputeCol {   // a c_ID / c_ID[k] column of thermo_style custom: a global compute (sf_global.hip)
+  std::string word, id;
+  long index = 0;
+  double value = 0.0;   // as printed in the last line
+};
+
 struct Thermo {
   // settings
   long long every = 0;                          // `thermo N` (LAMMPS default 0)
-  std::vector<int> keys = kStyleOne;
+  std::vector<int> keys = kStyleOne;            // < K_COUNT: a row of kKeys; K_COUNT + j: ccols[j]
+  std::vector<ComputeCol> ccols;
   bool norm_user = false, norm_value = false;   // thermo_modify norm (unset: by units)
   bool flush = false;
   bool lj = true;                               // units lj | si
@@ -257,7 +252,7 @@ struct Thermo {
   bool needs_virial() const
   {
     for (int k : keys)
-      if (kKeys[k].virial) return true;
+      if (k < K_COUNT && kKeys[k].virial) return true;
     return false;
   }
 };
@@ -316,7 +311,7 @@ void header(const SfLammps& L, Thermo& T)
 {
   std::string h;
   for (int k : T.keys) {
-    h += kKeys[k].header;
+    h += k < K_COUNT ? std::string(kKeys[k].header) : T.ccols[k - K_COUNT].word;   // ([3P] a compute column: the word as typed)
     h += ' ';
   }
   h += '\n';
@@ -365,6 +360,27 @@ void reduce(SfLammps& L, Thermo& T, double K[6], double* f2, double* fmax, doubl
   *fmax = m;
 }
 
+// the c_ columns against the computes as they stand ([3P] Thermo::parse_fields wording); at the thermo_style line and at
+// every line (a compute may have been removed since)
+void check_compute_cols(const SfLammps& L, const std::vector<ComputeCol>& cols)
+{
+  if (cols.empty()) return;
+  if (L.world_size > 1 || L.decomposed || L.eng.nranks() > 1 || L.eng.decomposed())
+    fail("thermo_style custom: c_ columns on one rank only (no decomposed domain)");
+  for (const ComputeCol& c : cols) {
+    bool vec = false;
+    const int n = global_compute_nvalues(L, c.id, &vec);
+    if (n == 0) {
+      if (atom_compute_ncols(L, c.id) > 0 || pair_local_exists(L, c.id))
+        fail(c.index == 0 ? "Thermo compute does not compute scalar" : "Thermo compute does not compute vector");
+      fail("Could not find thermo custom compute ID: %s", c.id.c_str());
+    }
+    if (c.index == 0 && vec) fail("Thermo compute does not compute scalar");
+    if (c.index > 0 && !vec) fail("Thermo compute does not compute vector");
+    if (c.index > n) fail("Thermo compute vector is accessed out-of-range");
+  }
+}
+
 void line(SfLammps& L, Thermo& T)
 {
   DemEngine& e = L.eng;
@@ -406,12 +422,26 @@ void line(SfLammps& L, Thermo& T)
   for (int c = 0; c < 6; c++) v[K_PXX + c] = (K[c] + W[c]) / V;
   v[K_FMAX] = fmax;
   v[K_FNORM] = std::sqrt(f2);
+  if (!T.ccols.empty()) {
+    // the columns of one compute share one copy; extensive values / natoms under norm yes ([3P] Thermo::compute_compute)
+    check_compute_cols(L, T.ccols);
+    std::vector<double> vals;
+    for (size_t j = 0; j < T.ccols.size(); j++) {
+      ComputeCol& cc = T.ccols[j];
+      if (j == 0 || T.ccols[j - 1].id != cc.id) global_values_host(L, cc.id, &vals);
+      bool vec = false, ext = false;
+      global_compute_nvalues(L, cc.id, &vec, &ext);
+      cc.value = vals[cc.index > 0 ? cc.index - 1 : 0];
+      if (ext && T.norm() && N > 0.0) cc.value /= N;
+    }
+  }
   T.have_line = true;
   T.last_line = step;
   std::string s;
   char b[64];
   for (int k : T.keys) {
-    if (kKeys[k].integer) snprintf(b, sizeof(b), "%8ld ", (long)v[k]);
+    if (k >= K_COUNT) snprintf(b, sizeof(b), "%12.8g ", T.ccols[k - K_COUNT].value);
+    else if (kKeys[k].integer) snprintf(b, sizeof(b), "%8ld ", (long)v[k]);
     else snprintf(b, sizeof(b), "%12.8g ", v[k]);
     s += b;
   }
@@ -517,6 +547,7 @@ bool thermo_command(SfLammps& L, const std::vector<std::string>& w)
   } else if (c == "thermo_style") {
     if (w.size() < 2) fail("Illegal thermo_style command");
     std::vector<int> keys;
+    std::vector<ComputeCol> ccols;
     if (w[1] == "one") {
       if (w.size() != 2) fail("Illegal thermo_style command");
       keys = kStyleOne;
@@ -527,14 +558,24 @@ bool thermo_command(SfLammps& L, const std::vector<std::string>& w)
       for (size_t a = 2; a < w.size(); a++) {
         int k = 0;
         while (k < K_COUNT && w[a] != kKeys[k].name) k++;
-        if (k == K_COUNT) fail("Invalid keyword in thermo_style custom command: %s", w[a].c_str());
+        if (k == K_COUNT && w[a].compare(0, 2, "c_") == 0) {   // a global compute
+          ComputeCol cc;
+          cc.word = w[a];
+          const std::string err = parse_thermo_column(w[a], &cc.id, &cc.index);
+          if (!err.empty()) fail("%s", err.c_str());
+          k = K_COUNT + (int)ccols.size();
+          ccols.push_back(cc);
+        } else if (k == K_COUNT)
+          fail("Invalid keyword in thermo_style custom command: %s", w[a].c_str());
         keys.push_back(k);
       }
+      check_compute_cols(L, ccols);
     } else {
       fail("Illegal thermo_style command: style %s", w[1].c_str());
     }
     Thermo& T = ensure(L);
     T.keys = keys;
+    T.ccols = ccols;
     T.norm_user = false;   // [3P] a new Thermo: norm and flush back to their defaults
     T.flush = false;
   } else if (c == "thermo_modify") {
@@ -587,7 +628,7 @@ bool thermo_needs_dof(const SfLammps& L)
   const Thermo* T = get(L);
   if (!T) return false;
   for (int k : T->keys)
-    if (k == K_TEMP || k == K_PRESS || k == K_KE || k == K_ETOTAL || kKeys[k].virial) return true;
+    if (k == K_TEMP || k == K_PRESS || k == K_KE || k == K_ETOTAL || (k < K_COUNT && kKeys[k].virial)) return true;
   return false;
 }
 
@@ -660,8 +701,41 @@ void thermo_run_end(SfLammps& L)
   if (T.log) fflush(T.log);
 }
 
+std::vector<std::string> thermo_global_ids_due(const SfLammps& L, bool setup, int run_n)
+{
+  std::vector<std::string> ids;
+  const Thermo* T = get(L);
+  if (!T || T->ccols.empty() || !thermo_active(L)) return ids;
+  const long long step = L.eng.nsteps();
+  const long long last = setup ? step + (run_n > 0 ? run_n : 0) : T->run_last;
+  if (!setup && (step == T->last_line || !(step == last || (T->every > 0 && step % T->every == 0)))) return ids;
+  for (const ComputeCol& c : T->ccols)
+    if (std::find(ids.begin(), ids.end(), c.id) == ids.end()) ids.push_back(c.id);
+  return ids;
+}
+
+bool thermo_uses_compute(const SfLammps& L, const std::string& id)
+{
+  const Thermo* T = get(L);
+  if (!T) return false;
+  for (const ComputeCol& c : T->ccols)
+    if (c.id == id) return true;
+  return false;
+}
+
 int thermo_get(const SfLammps& L, const std::string& keyword, double* v)
 {
+  if (keyword.compare(0, 2, "c_") == 0) {   // a compute column of the current style, by the word as typed
+    const Thermo* T = get(L);
+    if (T)
+      for (const ComputeCol& c : T->ccols)
+        if (c.word == keyword) {
+          if (!T->have_line) return -1;
+          *v = c.value;
+          return 0;
+        }
+    return -2;
+  }
   int k = 0;
   while (k < K_COUNT && keyword != kKeys[k].name) k++;
   if (k == K_COUNT) return -2;

@@ -168,7 +168,8 @@ class Lammps:
 
     def compute_atom(self, cid):
         """the values of the per-atom compute `cid` (stress/atom: [n, 6] in the order xx yy zz xy xz yz; contact/atom,
-        ke/atom, erotate/sphere/atom: [n]) now, sorted by tag like get_state(); atoms outside the compute's group read 0.
+        ke/atom, erotate/sphere/atom: [n]; property/atom: [n] for one attribute, [n, k] for several) now, sorted by tag like
+        get_state(); atoms outside the compute's group read 0.
         What a `dump custom` column c_ID / c_ID[k] written at this moment holds.  Passive: the run goes on with the same bits"""
         cid = str(cid).encode()
         nc = C.c_int()
@@ -219,6 +220,45 @@ class Lammps:
         out = np.zeros(3)
         check(self.L.sf_lammps_ave_chunk_cost(self.ptr, str(fid).encode(), _p(out)))
         return float(out[0]), float(out[1]), float(out[2])
+
+    def compute_global(self, cid):
+        """the values of the global compute `cid` (compute reduce, ke, erotate/sphere) on the state as it stands: a float64
+        array, length 1 for a scalar; not normalised.  What a fix ave/time sample or a thermo column c_ID / c_ID[k] taken at
+        this moment holds.  Passive: the run goes on with the same bits"""
+        cid = str(cid).encode()
+        vec = C.c_int()
+        n = check(self.L.sf_lammps_compute_global(self.ptr, cid, 0, None, C.byref(vec)))
+        val = np.zeros(n)
+        m = check(self.L.sf_lammps_compute_global(self.ptr, cid, n, _p(val), C.byref(vec)))
+        assert m == n
+        return val
+
+    def ave_time(self, fid):
+        """the latest output of `fix fid group ave/time ...`: dict(step, values[nvalues], names (the value words as typed))
+        -- what the last line of the fix's file holds.  An error before the first output"""
+        fid = str(fid).encode()
+        step = C.c_longlong()
+        n = check(self.L.sf_lammps_ave_time(self.ptr, fid, 0, C.byref(step), None))
+        val = np.zeros(n)
+        m = check(self.L.sf_lammps_ave_time(self.ptr, fid, n, C.byref(step), _p(val)))
+        assert m == n
+        nb = check(self.L.sf_lammps_ave_time_names(self.ptr, fid, 0, None))
+        buf = C.create_string_buffer(nb)
+        check(self.L.sf_lammps_ave_time_names(self.ptr, fid, nb, buf))
+        return dict(step=step.value, values=val, names=buf.value.decode().split())
+
+    def global_launches(self):
+        """dict(launches, host_copies): kernel launches made for global computes and fix ave/time so far, and the
+        device-to-host copies made for them (outputs, thermo lines and queries; none at a sample that is not an output)"""
+        n = C.c_longlong(); h = C.c_longlong()
+        check(self.L.sf_lammps_global_launches(self.ptr, C.byref(n), C.byref(h)))
+        return dict(launches=n.value, host_copies=h.value)
+
+    def global_cost(self, cid):
+        """GPU ms of one fresh evaluation of the global compute `cid` now"""
+        ms = C.c_double()
+        check(self.L.sf_lammps_global_cost(self.ptr, str(cid).encode(), C.byref(ms)))
+        return ms.value
 
     def set_molecule(self, tags, mol):
         """molecule IDs of the atoms with these tags (what `read_data FILE fix ID NULL Molecules` reads from a file)"""
