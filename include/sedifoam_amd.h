@@ -194,6 +194,21 @@ int sf_lammps_global_launches(void *ptr, long long *launches, long long *host_co
 /* measurement (tools/global_cost.py): GPU ms of one fresh evaluation of global compute `id` now, from HIP events (the
  * per-atom computes behind its c_ inputs are evaluated before the clock starts) */
 int sf_lammps_global_cost(void *ptr, const char *id, double *ms);
+/* histograms (`fix ID group ave/histo Nevery Nrepeat Nfreq lo hi Nbin value ... [mode scalar|vector] [kind global|peratom|
+ * local] [beyond ignore|end|extra] [ave one|running|window M] [start N] [file NAME] [overwrite] [title1|2|3 STRING]`,
+ * `unfix ID`): the latest output of fix `id` -- what the last block of the fix's file holds.  *step its step, stats4 =
+ * {total, missing, min, max}, coord[nbins] the bin coordinates and count[nbins] the counts (whole numbers).  Returns nbins
+ * (Nbin, or Nbin + 2 under beyond extra), or -1 (sf_last_error; also before the first output: "has made no output yet");
+ * with max = 0 (to size the arrays) or smaller than nbins nothing is written to coord and count. */
+long long sf_lammps_ave_histo(void *ptr, const char *id, long long max, long long *step, double *stats4, double *coord,
+                              double *count);
+/* binning launches made for fix ave/histo so far (one per fix and sample; local inputs: one per compute pair/local
+ * named), and *host_copies (may be NULL) the device-to-host copies: one per output, none at a sample that is not one */
+int sf_lammps_ave_histo_launches(void *ptr, long long *launches, long long *host_copies);
+/* measurement (tools/ave_histo_cost.py): GPU ms of the binning of one sample of fix `id` now, from HIP events; what its
+ * columns read (per-atom computes, contact rows, global computes) is evaluated before the clock starts.  Passive: the
+ * counts go to a buffer of their own, the fix's counters are untouched */
+int sf_lammps_ave_histo_cost(void *ptr, const char *id, double *ms);
 /* library.h:61-63 (particle injection / removal; tag[] is double in the reference) */
 int sf_lammps_create_particle(void *ptr, int npAdd, const double *position, const double *tag,
                               double diameter, double rho, int type, const double *vel);

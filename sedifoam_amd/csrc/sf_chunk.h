@@ -21,7 +21,7 @@ void chunk_invalidate(SfLammps& L);
 // `fix ID group ave/chunk ...` from the whole line (its title keywords may be quoted)
 void ave_chunk_fix_command(SfLammps& L, const std::string& line);
 bool ave_chunk_fix_exists(const SfLammps& L, const std::string& id);
-// `unfix ID`: a fix ave/chunk, or a fix ave/time (sf_global.hip)
+// `unfix ID`: a fix ave/chunk, a fix ave/time (sf_global.hip) or a fix ave/histo (sf_histo.hip)
 void unfix_command(SfLammps& L, const std::vector<std::string>& w);
 // does a fix ave/chunk name this compute (as its chunk compute or as a c_ value)?
 bool ave_chunk_uses_compute(const SfLammps& L, const std::string& id);

@@ -37,6 +37,7 @@
 #include "sf_contacts.h"
 #include "sf_global.h"
 #include "sf_handles.h"
+#include "sf_histo.h"
 
 namespace sf {
 namespace {
@@ -614,7 +615,7 @@ void ave_chunk_fix_command(SfLammps& L, const std::string& line)
   refuse_decomposed(L, "fix ave/chunk");
   F->groupbit = L.eng.group_bit(F->S.group);
   ChunkSet& T = ensure_set(L);
-  if (T.find_fix(F->S.id) || ave_time_fix_exists(L, F->S.id))
+  if (T.find_fix(F->S.id) || ave_time_fix_exists(L, F->S.id) || ave_histo_fix_exists(L, F->S.id))
     fail("fix ave/chunk %s: this fix ID is in use (unfix it first)", F->S.id.c_str());
   ChunkCompute* c = T.find(F->S.chunk);
   if (!c) {
@@ -660,8 +661,8 @@ void unfix_command(SfLammps& L, const std::vector<std::string>& w)
         T->fixes.erase(T->fixes.begin() + k);   // (closes its file)
         return;
       }
-  if (ave_time_unfix(L, w[1])) return;
-  fail("unfix %s: only a fix ave/chunk can be removed (or a fix ave/time), and there is none with this ID (the other fixes "
+  if (ave_time_unfix(L, w[1]) || ave_histo_unfix(L, w[1])) return;
+  fail("unfix %s: only a fix ave/chunk can be removed (or a fix ave/time or ave/histo), and there is none with this ID (the other fixes "
        "stay for the whole script)", w[1].c_str());
 }
 

@@ -40,6 +40,7 @@
 #include "sf_dump_fmt.h"
 #include "sf_global.h"
 #include "sf_handles.h"
+#include "sf_histo.h"
 #include "sf_thermo.h"
 
 namespace sf {
@@ -323,6 +324,8 @@ bool compute_command(SfLammps& L, const std::vector<std::string>& w)
     if (const char* who = global_uses_compute(L, w[1]))
       fail("uncompute %s: a %s still uses this compute (%s it first)", w[1].c_str(), who,
            who[0] == 'f' ? "unfix" : "uncompute");
+    if (ave_histo_uses_compute(L, w[1]))
+      fail("uncompute %s: a fix ave/histo still uses this compute (unfix it first)", w[1].c_str());
     if (global) {
       if (thermo_uses_compute(L, w[1]))
         fail("uncompute %s: thermo_style custom still names this compute (give another thermo_style first)", w[1].c_str());

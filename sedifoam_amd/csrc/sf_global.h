@@ -22,6 +22,9 @@ const char* global_uses_compute(const SfLammps& L, const std::string& id);
 void global_invalidate(SfLammps& L);
 // the values of `id` on the state as it stands, on the host (evaluated first when they are stale; one copy, one wait)
 void global_values_host(SfLammps& L, const std::string& id, std::vector<double>* out);
+// ... and where they lie on the device (evaluated first when they are stale; no copy, no wait): nvalues doubles that stay
+// at this address while the compute exists (fix ave/histo bins them there, sf_histo.hip)
+const double* global_values_device(SfLammps& L, const std::string& id);
 
 // ---- the fix ----
 // `fix ID group ave/time ...` from the whole line (its title keywords may be quoted)
@@ -35,6 +38,7 @@ bool ave_time_active(const SfLammps& L);
 // the first step after `step` at which some fix ave/time samples (-1: none)
 long long ave_time_next_step(const SfLammps& L, long long step);
 // One evaluation plan for the engine's current step: the computes of the fix ave/time samples due now and those named in
-// `also` (the c_ columns of a thermo line due now), each evaluated once; then the samples and outputs of the fixes
+// `also` (the c_ columns of a thermo line due now, the global inputs of the fix ave/histo samples due now), each evaluated
+// once; then the samples and outputs of the fixes
 void global_step_due(SfLammps& L, const std::vector<std::string>& also);
 }  // namespace sf

@@ -38,9 +38,11 @@
 #include "sf_chunk.h"
 #include "sf_compute_atom.h"
 #include "sf_contacts.h"
+#include "sf_gather_col.h"
 #include "sf_global.h"
 #include "sf_global_parse.h"
 #include "sf_handles.h"
+#include "sf_histo.h"
 
 // (a*a + s stays a product and a sum, so that a column's bits do not depend on what the compiler fuses around it)
 #pragma clang fp contract(off)
@@ -54,35 +56,12 @@ constexpr int kGMaxBlocks = 1024;   // partial rows
 constexpr int kGAcc = 24;           // accumulator additions one fold launch carries
 constexpr int kPool = 4096;         // device doubles: the values of the computes and the accumulators of the fixes
 
-enum GSrc { GS_XR, GS_VM, GS_OM, GS_FORCE, GS_TORQUE, GS_PTR, GS_INT, GS_ZERO, GS_ONE, GS_KE, GS_EROT };
 enum GOp { GO_SUM, GO_SUMSQ, GO_MIN, GO_MAX };
-enum GNeed { GN_XR = 1, GN_VM = 2, GN_OM = 4, GN_FORCE = 8, GN_TORQUE = 16, GN_MASK = 32 };
 
-struct GCol {
-  const void* p;   // GS_PTR: doubles indexed by element; GS_INT: ints
-  int code;        // src | comp << 8 | op << 16 (comp: x y z w of a record); packed: the table lives in scalar registers
-  int groupbit;    // 0: every element (rows)
-  __host__ __device__ int src() const { return code & 255; }
-  __host__ __device__ int comp() const { return (code >> 8) & 255; }
-  __host__ __device__ int op() const { return code >> 16; }
-  void set(int src, int comp, int op) { code = src | comp << 8 | op << 16; }
-};
-GCol make_col(const void* p, int src, int comp, int groupbit, int op)
-{
-  GCol c;
-  c.p = p;
-  c.groupbit = groupbit;
-  c.set(src, comp, op);
-  return c;
-}
 struct GTable {
   int n;
   unsigned need;
   GCol c[kGCols];
-};
-struct GRecords {
-  const double4 *xr, *vm, *om, *force, *torque;
-  const int* mask;
 };
 struct GFold {
   int n;
@@ -104,7 +83,6 @@ __device__ __forceinline__ double g_combine(int op, double a, double b)
 {
   return op == GO_MIN ? fmin(a, b) : (op == GO_MAX ? fmax(a, b) : a + b);
 }
-__device__ __forceinline__ double g_comp(const double4& a, int c) { return c == 0 ? a.x : (c == 1 ? a.y : (c == 2 ? a.z : a.w)); }
 
 __global__ __launch_bounds__(kGBlock) void k_global_gather(GRecords R, GTable T, long long n, double* partial)
 {
@@ -127,20 +105,7 @@ __global__ __launch_bounds__(kGBlock) void k_global_gather(GRecords R, GTable T,
       if (q < T.n) {
         const GCol c = T.c[q];
         if (c.groupbit == 0 || (mask & c.groupbit)) {
-          double v;
-          switch (c.src()) {
-            case GS_XR: v = g_comp(xr, c.comp()); break;
-            case GS_VM: v = g_comp(vm, c.comp()); break;
-            case GS_OM: v = g_comp(om, c.comp()); break;
-            case GS_FORCE: v = g_comp(f, c.comp()); break;
-            case GS_TORQUE: v = g_comp(tq, c.comp()); break;
-            case GS_PTR: v = static_cast<const double*>(c.p)[i]; break;
-            case GS_INT: v = (double)static_cast<const int*>(c.p)[i]; break;
-            case GS_ONE: v = 1.0; break;
-            case GS_KE: v = atom_ke_term(vm); break;
-            case GS_EROT: v = atom_erotate_term(vm, om, xr.w); break;
-            default: v = 0.0; break;
-          }
+          double v = g_value(c, i, xr, vm, om, f, tq);
           if (c.op() == GO_SUMSQ) v = v * v;
           acc[q] = g_combine(c.op(), acc[q], v);
         }
@@ -389,22 +354,6 @@ GOp op_of(int mode)
     case GM_AVESQ: return GO_SUMSQ;
     default: return GO_SUM;
   }
-}
-
-unsigned need_of(const GCol& c)
-{
-  unsigned need = c.groupbit ? GN_MASK : 0u;
-  switch (c.src()) {
-    case GS_XR: need |= GN_XR; break;
-    case GS_VM:
-    case GS_KE: need |= GN_VM; break;
-    case GS_OM: need |= GN_OM; break;
-    case GS_FORCE: need |= GN_FORCE; break;
-    case GS_TORQUE: need |= GN_TORQUE; break;
-    case GS_EROT: need |= GN_XR | GN_VM | GN_OM; break;
-    default: break;
-  }
-  return need;
 }
 
 // gather + fold of up to kGCols columns (count columns included) over n elements
@@ -745,6 +694,15 @@ void global_values_host(SfLammps& L, const std::string& id, std::vector<double>*
   out->assign(G->h_buf, G->h_buf + c->nvalues);
 }
 
+const double* global_values_device(SfLammps& L, const std::string& id)
+{
+  GlobalSet* G = set_of(L);
+  GlobalCompute* c = G ? G->find(id) : nullptr;
+  if (!c) fail("Could not find compute ID %s", id.c_str());
+  evaluate(L, *G, {c}, {});
+  return G->pool + c->slot;
+}
+
 // ---- the fix ----
 
 void ave_time_fix_command(SfLammps& L, const std::string& line)
@@ -758,7 +716,7 @@ void ave_time_fix_command(SfLammps& L, const std::string& line)
   refuse_decomposed(L, "fix ave/time");
   (void)L.eng.group_bit(F->S.group);   // (the group must exist; it is not used, as in LAMMPS)
   GlobalSet& G = ensure_set(L);
-  if (G.find_fix(F->S.id) || ave_chunk_fix_exists(L, F->S.id))
+  if (G.find_fix(F->S.id) || ave_chunk_fix_exists(L, F->S.id) || ave_histo_fix_exists(L, F->S.id))
     fail("fix ave/time %s: this fix ID is in use (unfix it first)", F->S.id.c_str());
   for (const AveTimeValue& v : F->S.values) check_fix_value(L, v);
   hipStream_t st = L.eng.stream();

@@ -47,11 +47,15 @@ struct SfLammps {
   // the global computes, the fix ave/time commands, their device values, accumulators and files (sf_global.hip); opaque like halo
   void* globals = nullptr;
   void (*globals_delete)(void*) = nullptr;
+  // the fix ave/histo commands, their device counters and files (sf_histo.hip); opaque like halo
+  void* histos = nullptr;
+  void (*histos_delete)(void*) = nullptr;
   ~SfLammps()
   {
     if (restart && restart_delete) restart_delete(restart);
     if (thermo && thermo_delete) thermo_delete(thermo);   // (closes the log and screen files)
     if (dumps && dumps_delete) dumps_delete(dumps);   // (drains the writer: the frames are in their files)
+    if (histos && histos_delete) histos_delete(histos);   // (closes the files of fix ave/histo)
     if (globals && globals_delete) globals_delete(globals);   // (closes the files of fix ave/time)
     if (chunks && chunks_delete) chunks_delete(chunks);   // (closes the files of fix ave/chunk; after the dumps, like computes)
     if (computes && computes_delete) computes_delete(computes);   // (after the dumps, whose frames read its rows)

@@ -22,6 +22,7 @@
 #include "sf_env.h"
 #include "sf_global.h"
 #include "sf_handles.h"
+#include "sf_histo.h"
 #include "sf_restart.h"
 #include "sf_rigid.h"
 #include "sf_roctx.h"
@@ -152,17 +153,17 @@ void advance(SfLammps& L, int n)
 // queued batch ends there with the end-of-step state: sub-step s with last = 1, then the dump kernels / the thermo
 // reduction, then the next piece begins with its initial integrate -- what consecutive `run N pre no post no` calls do),
 // and the frame of the current step is written first if it is due ([3P] Output::setup: step 0 at the setup of the first
-// run).  A fix ave/chunk cuts the run at its sample steps in the same way (sf_chunk.hip).  Without a dump, a thermo
+// run).  A fix ave/chunk, ave/time or ave/histo cuts the run at its sample steps in the same way.  Without a dump, a thermo
 // destination, a restart schedule or such a fix the run is not cut.
 void sf::run_steps(SfLammps& L, int n)
 {
   const bool thermo = sf::thermo_active(L), rst = sf::restart_active(L), avc = sf::ave_chunk_active(L);
-  const bool avt = sf::ave_time_active(L);
+  const bool avt = sf::ave_time_active(L), avh = sf::ave_histo_active(L);
   if (thermo && L.eng.rigid_on() && sf::thermo_needs_dof(L))
     sf::fail("thermo output with temp / press / ke / etotal / p** needs the degrees of freedom of the rigid bodies, which "
              "fix rigid/nve does not keep yet: use thermo_style custom without them, or -screen none -log none");
   sf::restart_run_begin(L);   // (wall rows of a restart file that no fix claimed are dropped here; host only)
-  if (!sf::dump_active(L) && !thermo && !rst && !avc && !avt) {
+  if (!sf::dump_active(L) && !thermo && !rst && !avc && !avt && !avh) {
     L.eng.set_thermo_virial(false);
     advance(L, n);
     return;
@@ -171,8 +172,15 @@ void sf::run_steps(SfLammps& L, int n)
   advance(L, 0);   // (setup: the frame of the first step holds the forces of the setup evaluation)
   sf::dump_write_due(L);
   if (avc) sf::ave_chunk_sample_due(L);   // (a sample whose step is this one: fix ave/chunk samples at the setup of a run)
-  // the global computes of this step, one plan: the fix ave/time samples due and the c_ columns of the thermo line
-  if (avt || thermo) sf::global_step_due(L, sf::thermo_global_ids_due(L, true, n));
+  // the global computes of this step, one plan: the fix ave/time samples due, the c_ columns of the thermo line and the
+  // global inputs of the fix ave/histo samples due; then those samples bin the values where they lie on the device
+  auto globals_and_histos_due = [&](bool setup) {
+    std::vector<std::string> ids = sf::thermo_global_ids_due(L, setup, setup ? n : 0);
+    if (avh) sf::ave_histo_global_ids_due(L, &ids);
+    if (avt || thermo || !ids.empty()) sf::global_step_due(L, ids);
+    if (avh) sf::ave_histo_sample_due(L);
+  };
+  globals_and_histos_due(true);
   if (thermo) sf::thermo_setup(L, n);
   const long long end = L.eng.nsteps() + (n > 0 ? n : 0);
   while (L.eng.nsteps() < end) {
@@ -191,10 +199,14 @@ void sf::run_steps(SfLammps& L, int n)
       const long long nx = sf::ave_time_next_step(L, L.eng.nsteps());
       if (nx >= 0) next = std::min(next, nx);
     }
+    if (avh) {
+      const long long nx = sf::ave_histo_next_step(L, L.eng.nsteps());
+      if (nx >= 0) next = std::min(next, nx);
+    }
     advance(L, (int)(next - L.eng.nsteps()));
     sf::dump_write_due(L);
     if (avc) sf::ave_chunk_sample_due(L);
-    if (avt || thermo) sf::global_step_due(L, sf::thermo_global_ids_due(L, false, 0));
+    globals_and_histos_due(false);
     if (rst) sf::restart_write_due(L);
     if (thermo) sf::thermo_write_due(L);
   }
@@ -574,6 +586,8 @@ void command(SfLammps& L, const std::string& line)
     cmd_group(L, w);
   } else if (c == "fix" && w.size() > 3 && w[3] == "ave/time") {
     sf::ave_time_fix_command(L, line);   // (from the line: its titles and format may be quoted; sf_global.hip)
+  } else if (c == "fix" && w.size() > 3 && (w[3] == "ave/histo" || w[3] == "ave/histo/weight")) {
+    sf::ave_histo_fix_command(L, line);   // (from the line: its titles may be quoted; sf_histo.hip)
   } else if (c == "fix" && w.size() > 3 && w[3] == "ave/chunk") {
     sf::ave_chunk_fix_command(L, line);   // (from the line: its title keywords may be quoted; sf_chunk.hip)
   } else if (c == "fix") {

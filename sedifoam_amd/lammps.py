@@ -260,6 +260,35 @@ class Lammps:
         check(self.L.sf_lammps_global_cost(self.ptr, str(cid).encode(), C.byref(ms)))
         return ms.value
 
+    def ave_histo(self, fid):
+        """the latest output of `fix fid group ave/histo ...`: dict(step, nbins, total, missing, min, max, coord[nbins],
+        count[nbins], frac[nbins] (count / total, 0 when total is 0)) -- what the last block of the fix's file holds.  An
+        error before the first output"""
+        fid = str(fid).encode()
+        step = C.c_longlong()
+        stats = np.zeros(4)
+        n = check(self.L.sf_lammps_ave_histo(self.ptr, fid, 0, C.byref(step), _p(stats), None, None))
+        coord = np.zeros(n); count = np.zeros(n)
+        m = check(self.L.sf_lammps_ave_histo(self.ptr, fid, n, C.byref(step), _p(stats), _p(coord), _p(count)))
+        assert m == n
+        total = float(stats[0])
+        frac = count / total if total > 0.0 else np.zeros(n)
+        return dict(step=step.value, nbins=n, total=total, missing=float(stats[1]), min=float(stats[2]), max=float(stats[3]),
+                    coord=coord, count=count, frac=frac)
+
+    def ave_histo_launches(self):
+        """dict(launches, host_copies): binning launches made for fix ave/histo so far, and the device-to-host copies (one
+        per output; none at a sample that is not an output)"""
+        n = C.c_longlong(); h = C.c_longlong()
+        check(self.L.sf_lammps_ave_histo_launches(self.ptr, C.byref(n), C.byref(h)))
+        return dict(launches=n.value, host_copies=h.value)
+
+    def ave_histo_cost(self, fid):
+        """GPU ms of the binning of one sample of fix ave/histo `fid` now; passive"""
+        ms = C.c_double()
+        check(self.L.sf_lammps_ave_histo_cost(self.ptr, str(fid).encode(), C.byref(ms)))
+        return ms.value
+
     def set_molecule(self, tags, mol):
         """molecule IDs of the atoms with these tags (what `read_data FILE fix ID NULL Molecules` reads from a file)"""
         t, m = _i32(tags), _i32(mol)
