@@ -17,19 +17,11 @@ void chunk_compute_remove(SfLammps& L, const std::string& id);
 const double* chunk_compute_values(SfLammps& L, const std::string& id);
 void chunk_invalidate(SfLammps& L);
 
-// ---- the fix ----
+// ---- the fix (its ID space, unfix and the run's cuts: sf_ave_fix.h) ----
 // `fix ID group ave/chunk ...` from the whole line (its title keywords may be quoted)
 void ave_chunk_fix_command(SfLammps& L, const std::string& line);
-bool ave_chunk_fix_exists(const SfLammps& L, const std::string& id);
-// `unfix ID`: a fix ave/chunk, a fix ave/time (sf_global.hip) or a fix ave/histo (sf_histo.hip)
-void unfix_command(SfLammps& L, const std::vector<std::string>& w);
-// does a fix ave/chunk name this compute (as its chunk compute or as a c_ value)?
-bool ave_chunk_uses_compute(const SfLammps& L, const std::string& id);
 
-// ---- the run (sf::run_steps) ----
-bool ave_chunk_active(const SfLammps& L);
-// the first step after `step` at which some fix ave/chunk samples (-1: none)
-long long ave_chunk_next_step(const SfLammps& L, long long step);
+// ---- the run (ave_fix_step_due of sf_ave_fix.hip) ----
 // the samples (and outputs) due at the engine's current step that were not taken yet
 void ave_chunk_sample_due(SfLammps& L);
 }  // namespace sf

@@ -26,18 +26,15 @@
 #include <string>
 #include <vector>
 
-#include <unistd.h>
-
 #include <hip/hip_runtime.h>
 
 #include "../../include/sedifoam_amd.h"
+#include "sf_ave_fix.h"
 #include "sf_chunk.h"
 #include "sf_chunk_parse.h"
 #include "sf_compute_atom.h"
 #include "sf_contacts.h"
 #include "sf_global.h"
-#include "sf_handles.h"
-#include "sf_histo.h"
 
 namespace sf {
 namespace {
@@ -230,27 +227,16 @@ struct ChunkCompute {
   int nlocal = -1, gnlocal = -1;
 };
 
-struct AveFix {
+struct AveFix : AveFixState {
   AveSpec S;
   int groupbit = 1;
   int nchunk = 0, ncol = 1;
-  long long nvalid = 0;
-  int irepeat = 0;
   Grown partial, acc, cost_acc;
   std::vector<double> h_acc;
   // ave running: the sums of norm all (device layout) and the sums of the per-output results, over noutputs outputs
   std::vector<double> run_acc, run_res;
   long long noutputs = 0;
-  // the latest output
-  bool have = false;
-  long long out_step = -1;
-  std::vector<double> count, values;   // [nchunk], row-major [nchunk][nvalues]
-  FILE* fp = nullptr;
-  long filepos = 0;
-  ~AveFix()
-  {
-    if (fp) fclose(fp);
-  }
+  std::vector<double> count, values;   // the latest output: [nchunk], row-major [nchunk][nvalues]
 };
 
 struct ChunkSet {
@@ -263,12 +249,7 @@ struct ChunkSet {
       if (c->id == id) return c.get();
     return nullptr;
   }
-  AveFix* find_fix(const std::string& id)
-  {
-    for (auto& f : fixes)
-      if (f->S.id == id) return f.get();
-    return nullptr;
-  }
+  AveFix* find_fix(const std::string& id) const { return ave_find(fixes, id); }
 };
 
 ChunkSet* set_of(const SfLammps& L) { return static_cast<ChunkSet*>(L.chunks); }
@@ -279,13 +260,6 @@ ChunkSet& ensure_set(SfLammps& L)
     L.chunks_delete = [](void* p) { delete static_cast<ChunkSet*>(p); };
   }
   return *set_of(L);
-}
-
-void refuse_decomposed(const SfLammps& L, const char* who)
-{
-  const DemEngine& e = L.eng;
-  if (L.world_size > 1 || L.decomposed || e.nranks() > 1 || e.decomposed())
-    fail("%s: one rank only (no decomposed domain)", who);
 }
 
 bool assigned_now(const SfLammps& L, const ChunkCompute& c)
@@ -445,27 +419,24 @@ void chunk_coords(const ChunkBins& B, int chunk0, double* xyz)   // chunk0 = chu
 
 void write_output(AveFix& F, const ChunkBins& B)
 {
-  if (!F.fp) return;
+  FILE* fp = F.file.fp();
+  if (!fp) return;
   const int nv = (int)F.S.values.size();
-  if (F.S.overwrite && fseek(F.fp, F.filepos, SEEK_SET) != 0) fail("fix ave/chunk %s: cannot rewind %s", F.S.id.c_str(), F.S.file.c_str());
+  fail_if(F.file.begin_block());
   double total = 0.0;
   for (int c = 0; c < F.nchunk; c++) total += F.count[c];
   const std::string vfmt = " " + (F.S.format.empty() ? std::string("%g") : F.S.format);
-  fprintf(F.fp, "%lld %d %g\n", F.out_step, F.nchunk, total);
+  fprintf(fp, "%lld %d %g\n", F.out_step, F.nchunk, total);
   double xyz[3];
   for (int c = 0; c < F.nchunk; c++) {
-    fprintf(F.fp, "  %d", c + 1);
+    fprintf(fp, "  %d", c + 1);
     chunk_coords(B, c, xyz);
-    for (int a = 0; a < B.ndim; a++) fprintf(F.fp, " %g", xyz[a]);
-    fprintf(F.fp, " %g", F.count[c]);
-    for (int j = 0; j < nv; j++) fprintf(F.fp, vfmt.c_str(), F.values[(size_t)c * nv + j]);
-    fputc('\n', F.fp);
+    for (int a = 0; a < B.ndim; a++) fprintf(fp, " %g", xyz[a]);
+    fprintf(fp, " %g", F.count[c]);
+    for (int j = 0; j < nv; j++) fprintf(fp, vfmt.c_str(), F.values[(size_t)c * nv + j]);
+    fputc('\n', fp);
   }
-  if (fflush(F.fp) != 0) fail("fix ave/chunk %s: error writing %s", F.S.id.c_str(), F.S.file.c_str());
-  if (F.S.overwrite) {
-    const long end = ftell(F.fp);
-    if (end < 0 || ftruncate(fileno(F.fp), end) != 0) fail("fix ave/chunk %s: cannot truncate %s", F.S.id.c_str(), F.S.file.c_str());
-  }
+  fail_if(F.file.end_block());
 }
 
 // the accumulator of Nrepeat samples -> Ncount and the value columns of one output (the rules of DESIGN.md section 14)
@@ -525,30 +496,47 @@ void sample(SfLammps& L, ChunkSet& T, AveFix& F)
   ChunkCompute& c = chunk_of(T, F);
   group(L, T, c);
   launch_sums(L, T, F, c, F.acc.as<double>());
-  F.irepeat++;
-  const long long step = L.eng.nsteps();
-  if (F.irepeat < F.S.nrepeat) {
-    F.nvalid = step + F.S.nevery;
-    return;
-  }
-  F.irepeat = 0;
-  F.nvalid = step + F.S.nfreq - (F.S.nrepeat - 1) * F.S.nevery;
-  make_output(L, F, c.B);
+  if (F.S.sampled(L.eng.nsteps())) make_output(L, F, c.B);
 }
 
-// a fix whose sample step has passed without a sample (steps taken outside run_steps): begin a new output
-void catch_up(SfLammps& L, AveFix& F)
+bool fix_exists(const SfLammps& L, const std::string& id)
 {
-  const long long step = L.eng.nsteps();
-  if (F.nvalid >= step) return;
-  F.nvalid = ave_first_valid(step, F.S.nevery, F.S.nrepeat, F.S.nfreq);
-  if (F.irepeat > 0) {
-    F.irepeat = 0;
-    SF_HIP(hipMemsetAsync(F.acc.p, 0, sizeof(double) * (size_t)F.ncol * (size_t)F.nchunk, L.eng.stream()));
+  ChunkSet* T = set_of(L);
+  return T && T->find_fix(id);
+}
+
+bool unfix(SfLammps& L, const std::string& id)
+{
+  ChunkSet* T = set_of(L);
+  return T && ave_take(L, T->fixes, id);
+}
+
+// does a fix ave/chunk name this compute (as its chunk compute or as a c_ value)?
+bool uses_compute(const SfLammps& L, const std::string& id)
+{
+  const ChunkSet* T = set_of(L);
+  if (!T) return false;
+  for (const auto& f : T->fixes) {
+    if (f->S.chunk == id) return true;
+    for (const AveValue& v : f->S.values)
+      if (v.source == AS_COMPUTE && v.id == id) return true;
   }
+  return false;
+}
+
+long long next_step(const SfLammps& L, long long step)
+{
+  const ChunkSet* T = set_of(L);
+  return T ? ave_next(T->fixes, step) : -1;
 }
 
 }  // namespace
+
+const AveFixKind& ave_chunk_kind()
+{
+  static const AveFixKind kind = {"fix ave/chunk", fix_exists, unfix, uses_compute, next_step};
+  return kind;
+}
 
 // ---- the compute ----
 
@@ -610,12 +598,11 @@ void ave_chunk_fix_command(SfLammps& L, const std::string& line)
   const std::string qerr = split_quoted(line, &w);
   if (!qerr.empty()) fail("%s", qerr.c_str());
   auto F = std::make_unique<AveFix>();
-  const std::string err = parse_ave_chunk(w, &F->S);
-  if (!err.empty()) fail("%s", err.c_str());
+  fail_if(parse_ave_chunk(w, &F->S));
   refuse_decomposed(L, "fix ave/chunk");
   F->groupbit = L.eng.group_bit(F->S.group);
   ChunkSet& T = ensure_set(L);
-  if (T.find_fix(F->S.id) || ave_time_fix_exists(L, F->S.id) || ave_histo_fix_exists(L, F->S.id))
+  if (ave_fix_exists(L, F->S.id))
     fail("fix ave/chunk %s: this fix ID is in use (unfix it first)", F->S.id.c_str());
   ChunkCompute* c = T.find(F->S.chunk);
   if (!c) {
@@ -627,79 +614,18 @@ void ave_chunk_fix_command(SfLammps& L, const std::string& line)
     if (v.source == AS_COMPUTE) check_compute_value(L, v);
   F->nchunk = c->B.nchunk;
   F->ncol = 1 + (int)F->S.values.size();
-  const long long step = L.eng.nsteps();
-  F->nvalid = ave_first_valid(step, F->S.nevery, F->S.nrepeat, F->S.nfreq);
+  F->S.begin(L.eng.nsteps());
   hipStream_t st = L.eng.stream();
   const size_t na = sizeof(double) * (size_t)F->ncol * (size_t)F->nchunk;
   F->acc.get(na, st);
   SF_HIP(hipMemsetAsync(F->acc.p, 0, na, st));
-  if (!F->S.file.empty()) {
-    F->fp = fopen(F->S.file.c_str(), "w+");
-    if (!F->fp) fail("Cannot open fix ave/chunk file %s", F->S.file.c_str());
-    std::string t3 = "# Chunk";
-    for (int a = 0; a < c->B.ndim; a++) t3 += " Coord" + std::to_string(a + 1);
-    t3 += " Ncount";
-    for (const AveValue& v : F->S.values) t3 += " " + v.word;
-    const std::string t1 = "# Chunk-averaged data for fix " + F->S.id + " and group " + F->S.group;
-    const std::string t2 = "# Timestep Number-of-chunks Total-count";
-    fprintf(F->fp, "%s\n%s\n%s\n", (F->S.has_title[0] ? F->S.title[0] : t1).c_str(), (F->S.has_title[1] ? F->S.title[1] : t2).c_str(),
-            (F->S.has_title[2] ? F->S.title[2] : t3).c_str());
-    fflush(F->fp);
-    F->filepos = ftell(F->fp);
-  }
+  std::string titles[3] = {"# Chunk-averaged data for fix " + F->S.id + " and group " + F->S.group,
+                           "# Timestep Number-of-chunks Total-count", "# Chunk"};
+  for (int a = 0; a < c->B.ndim; a++) titles[2] += " Coord" + std::to_string(a + 1);
+  titles[2] += " Ncount";
+  for (const AveValue& v : F->S.values) titles[2] += " " + v.word;
+  fail_if(F->file.open(F->S, "ave/chunk", F->S.id, titles, 3));
   T.fixes.push_back(std::move(F));
-}
-
-void unfix_command(SfLammps& L, const std::vector<std::string>& w)
-{
-  if (w.size() != 2) fail("Illegal unfix command");
-  ChunkSet* T = set_of(L);
-  if (T)
-    for (size_t k = 0; k < T->fixes.size(); k++)
-      if (T->fixes[k]->S.id == w[1]) {
-        SF_HIP(hipStreamSynchronize(L.eng.stream()));   // (a sample queued on the stream may still add into its accumulator)
-        T->fixes.erase(T->fixes.begin() + k);   // (closes its file)
-        return;
-      }
-  if (ave_time_unfix(L, w[1]) || ave_histo_unfix(L, w[1])) return;
-  fail("unfix %s: only a fix ave/chunk can be removed (or a fix ave/time or ave/histo), and there is none with this ID (the other fixes "
-       "stay for the whole script)", w[1].c_str());
-}
-
-bool ave_chunk_fix_exists(const SfLammps& L, const std::string& id)
-{
-  ChunkSet* T = set_of(L);
-  return T && T->find_fix(id);
-}
-
-bool ave_chunk_uses_compute(const SfLammps& L, const std::string& id)
-{
-  const ChunkSet* T = set_of(L);
-  if (!T) return false;
-  for (const auto& f : T->fixes) {
-    if (f->S.chunk == id) return true;
-    for (const AveValue& v : f->S.values)
-      if (v.source == AS_COMPUTE && v.id == id) return true;
-  }
-  return false;
-}
-
-bool ave_chunk_active(const SfLammps& L)
-{
-  const ChunkSet* T = set_of(L);
-  return T && !T->fixes.empty();
-}
-
-long long ave_chunk_next_step(const SfLammps& L, long long step)
-{
-  const ChunkSet* T = set_of(L);
-  long long best = -1;
-  if (!T) return best;
-  for (const auto& f : T->fixes) {
-    const long long nx = f->nvalid > step ? f->nvalid : ave_first_valid(step + 1, f->S.nevery, f->S.nrepeat, f->S.nfreq);
-    if (best < 0 || nx < best) best = nx;
-  }
-  return best;
 }
 
 void ave_chunk_sample_due(SfLammps& L)
@@ -708,20 +634,15 @@ void ave_chunk_sample_due(SfLammps& L)
   if (!T) return;
   const long long step = L.eng.nsteps();
   for (auto& f : T->fixes) {
-    catch_up(L, *f);
-    if (f->nvalid == step) sample(L, *T, *f);
+    if (f->S.catch_up(step))   // (the samples of the output that was under way are dropped)
+      SF_HIP(hipMemsetAsync(f->acc.p, 0, sizeof(double) * (size_t)f->ncol * (size_t)f->nchunk, L.eng.stream()));
+    if (f->S.due(step)) sample(L, *T, *f);
   }
 }
 
 }  // namespace sf
 
-namespace {
-sf::SfLammps* handle(void* p)
-{
-  if (!p) sf::fail("null engine handle");
-  return static_cast<sf::SfLammps*>(p);
-}
-}  // namespace
+using sf::handle;
 
 extern "C" {
 

@@ -2,12 +2,15 @@
 // bins they define and the sample schedule ([3P] LAMMPS names and rules: ComputeChunkAtom::setup_xyz_bins / atom2bin*,
 // FixAveChunk::FixAveChunk / nextvalid), on the host with nothing but the standard library, so that this code can be
 // compiled into a stand-alone program and run under the host sanitizers (sf_compute_parse.h is the precedent).  Every
-// parser returns an empty string, or the error text.
+// parser returns an empty string, or the error text.  The schedule, the file keywords and the c_ID[k] parser are those of
+// sf_ave_common.h; split_quoted, chunk_parse_double and ave_format_ok are here for the other parse headers.
 #pragma once
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
+
+#include "sf_ave_common.h"
 
 namespace sf {
 
@@ -41,14 +44,6 @@ inline bool chunk_parse_double(const std::string& s, double* v)
   char* end = nullptr;
   *v = std::strtod(s.c_str(), &end);
   return end != s.c_str() && *end == '\0' && *v == *v && *v - *v == 0.0;   // (a finite number, all of the word)
-}
-
-inline bool chunk_parse_int(const std::string& s, long* v)
-{
-  if (s.empty()) return false;
-  char* end = nullptr;
-  *v = std::strtol(s.c_str(), &end, 10);
-  return end != s.c_str() && *end == '\0' && *v > -2000000000L && *v < 2000000000L;
 }
 
 // The bins of a chunk/atom compute, per binned dimension k (the first one named varies slowest in the chunk ID); plain
@@ -260,16 +255,11 @@ struct AveValue {
   long index = 0;     // AS_COMPUTE: k of c_ID[k], 0: none
 };
 
-struct AveSpec {
+struct AveSpec : AveSchedule, AveFileSpec {
   std::string id, group, chunk;
-  long nevery = 1, nrepeat = 1, nfreq = 1;
   std::vector<AveValue> values;
   int norm = 0;          // 0 all, 1 sample, 2 none
   bool running = false;
-  std::string file;
-  bool overwrite = false;
-  bool has_title[3] = {false, false, false};
-  std::string title[3];
   std::string format;    // empty: %g
 };
 
@@ -299,9 +289,7 @@ inline std::string parse_ave_chunk(const std::vector<std::string>& w, AveSpec* o
   AveSpec S;
   S.id = w[1];
   S.group = w[2];
-  if (!chunk_parse_int(w[4], &S.nevery) || !chunk_parse_int(w[5], &S.nrepeat) || !chunk_parse_int(w[6], &S.nfreq)) return illegal;
-  if (S.nevery <= 0 || S.nrepeat <= 0 || S.nfreq <= 0) return illegal;
-  if (S.nfreq % S.nevery || S.nrepeat * S.nevery > S.nfreq) return illegal;
+  if (!S.parse(w, 4, illegal).empty()) return illegal;
   S.chunk = w[7];
   static const char* const plain[8] = {"vx", "vy", "vz", "fx", "fy", "fz", "density/number", "density/mass"};
   size_t k = 8;
@@ -320,17 +308,7 @@ inline std::string parse_ave_chunk(const std::vector<std::string>& w, AveSpec* o
       return "fix ave/chunk: " + s + " is not supported (f_ and v_ values are not; c_ID of a per-atom compute is)";
     else if (s.compare(0, 2, "c_") == 0) {
       v.source = AS_COMPUTE;
-      v.id = s.substr(2);
-      const size_t br = v.id.find('[');
-      if (br != std::string::npos) {
-        const char* first = v.id.c_str() + br + 1;
-        char* end = nullptr;
-        const long idx = std::strtol(first, &end, 10);
-        if (end == first || *end != ']' || end[1] || idx < 1 || idx > 1000000) return illegal;
-        v.index = idx;
-        v.id.resize(br);
-      }
-      if (v.id.empty()) return illegal;
+      if (!parse_cref(s, &v.id, &v.index)) return illegal;
     } else
       break;
     if ((int)S.values.size() >= kAveMaxValues) return "fix ave/chunk: more than 24 values";
@@ -340,6 +318,9 @@ inline std::string parse_ave_chunk(const std::vector<std::string>& w, AveSpec* o
   while (k < w.size()) {
     const std::string& key = w[k];
     const size_t left = w.size() - k - 1;
+    const AveKey fk = ave_file_keyword(w, &k, &S);
+    if (fk == AK_ERROR) return illegal;
+    if (fk == AK_CONSUMED) continue;
     if (key == "norm") {
       if (left < 1) return illegal;
       if (w[k + 1] == "all") S.norm = 0;
@@ -354,19 +335,6 @@ inline std::string parse_ave_chunk(const std::vector<std::string>& w, AveSpec* o
       else if (w[k + 1] == "window") return "fix ave/chunk: ave window is not supported (ave one and ave running are)";
       else return illegal;
       k += 2;
-    } else if (key == "file") {
-      if (left < 1 || w[k + 1].empty()) return illegal;
-      S.file = w[k + 1];
-      k += 2;
-    } else if (key == "overwrite") {
-      S.overwrite = true;
-      k += 1;
-    } else if (key == "title1" || key == "title2" || key == "title3") {
-      if (left < 1) return illegal;
-      const int t = key[5] - '1';
-      S.has_title[t] = true;
-      S.title[t] = w[k + 1];
-      k += 2;
     } else if (key == "format") {
       if (left < 1) return illegal;
       if (!ave_format_ok(w[k + 1]))
@@ -380,18 +348,6 @@ inline std::string parse_ave_chunk(const std::vector<std::string>& w, AveSpec* o
   }
   *out = S;
   return std::string();
-}
-
-// the first step >= t0 at which a fix defined at step t0 samples ([3P] FixAveChunk::nextvalid; with `start`, the keyword of
-// fix ave/time, [3P] FixAveTime::nextvalid: no output before step `start`)
-inline long long ave_first_valid(long long t0, long long nevery, long long nrepeat, long long nfreq, long long start = 0)
-{
-  long long nv = (t0 / nfreq) * nfreq + nfreq;
-  while (nv < start) nv += nfreq;
-  if (nv - nfreq == t0 && nrepeat == 1) nv = t0;
-  else nv -= (nrepeat - 1) * nevery;
-  if (nv < t0) nv += nfreq;
-  return nv;
 }
 
 }  // namespace sf

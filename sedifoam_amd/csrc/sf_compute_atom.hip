@@ -274,9 +274,7 @@ AtomSet& ensure_set(SfLammps& L)
 void refuse_unsupported(const SfLammps& L, Kind kind)
 {
   const DemEngine& e = L.eng;
-  const char* who = kStyleName[kind];
-  if (L.world_size > 1 || L.decomposed || e.nranks() > 1 || e.decomposed())
-    fail("compute %s: one rank only (no decomposed domain)", who);
+  refuse_decomposed(L, (std::string("compute ") + kStyleName[kind]).c_str());
   if (kind == K_STRESS) {
     if (e.pair_lubricate_on())
       fail("compute stress/atom: not with lubricate/poly in the pair style (its pair terms are not in the per-atom stress)");
@@ -427,34 +425,13 @@ double atom_compute_cost(SfLammps& L, const std::string& id)
   if (!c && chunk_compute_exists(L, id)) fail("compute %s is a chunk/atom compute: sf_lammps_ave_chunk_cost times its pass", id.c_str());
   if (!c) fail("Could not find compute ID %s", id.c_str());
   hipStream_t st = L.eng.stream();
-  hipEvent_t ev[2];
-  for (hipEvent_t& e : ev) SF_HIP(hipEventCreate(&e));
-  struct EvGuard {
-    hipEvent_t* ev;
-    ~EvGuard()
-    {
-      for (int k = 0; k < 2; k++) (void)hipEventDestroy(ev[k]);
-    }
-  } guard{ev};
   c->val.get(sizeof(double) * (size_t)c->ncols() * (size_t)std::max(L.eng.nlocal(), 1), st);   // (not in the time)
-  SF_HIP(hipEventRecord(ev[0], st));
-  evaluate(L, *T, *c);
-  SF_HIP(hipEventRecord(ev[1], st));
-  SF_HIP(hipStreamSynchronize(st));
-  float ms = 0.f;
-  SF_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-  return (double)ms;
+  return stream_ms(st, [&] { evaluate(L, *T, *c); });
 }
 
 }  // namespace sf
 
-namespace {
-sf::SfLammps* handle(void* p)
-{
-  if (!p) sf::fail("null engine handle");
-  return static_cast<sf::SfLammps*>(p);
-}
-}  // namespace
+using sf::handle;
 
 extern "C" {
 

@@ -4,30 +4,18 @@
 //   the keywords of `compute ID group stress/atom [NULL] [ke] ...`    ([3P] ComputeStressAtom::ComputeStressAtom)
 // Both return an empty string, or the error text.
 #pragma once
-#include <cstdlib>
 #include <string>
 #include <vector>
 
+#include "sf_ave_common.h"
+
 namespace sf {
 
-// `word` = c_ID or c_ID[k]: the ID and k (0: no index given).  The caller has seen the "c_" in front
+// `word` = c_ID or c_ID[k]: the ID and k (0: no index given), by parse_cref of sf_ave_common.h
 inline std::string parse_compute_column(const std::string& word, const char* dump_style, std::string* id, long* index)
 {
   const std::string bad = "Invalid attribute " + word + " in dump " + dump_style + " command";
-  if (word.size() < 3 || word.compare(0, 2, "c_") != 0) return bad;
-  *id = word.substr(2);
-  *index = 0;
-  const size_t br = id->find('[');
-  if (br != std::string::npos) {
-    const char* first = id->c_str() + br + 1;
-    char* end = nullptr;
-    const long k = std::strtol(first, &end, 10);
-    if (end == first || *end != ']' || end[1] || k < 1) return bad;
-    *index = k;
-    id->resize(br);
-  }
-  if (id->empty()) return bad;
-  return std::string();
+  return parse_cref(word, id, index) ? std::string() : bad;
 }
 
 // w[first ...]: the words behind `stress/atom`.  No keyword: ke and pair both; `virial` = `pair`; fix bond angle dihedral

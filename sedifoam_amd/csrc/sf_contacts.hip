@@ -39,8 +39,7 @@
 #include "sf_dem_dispatch.h"
 #include "sf_dump_fmt.h"
 #include "sf_global.h"
-#include "sf_handles.h"
-#include "sf_histo.h"
+#include "sf_ave_fix.h"
 #include "sf_thermo.h"
 
 namespace sf {
@@ -298,8 +297,7 @@ void refuse_unsupported(const SfLammps& L, const char* who)
     fail("%s: No pair style is defined for compute pair/local (a granular pair style is needed)", who);
   if (e.rigid_on())
     fail("%s: not while fix rigid/nve exists (the pair law then takes the masses of the bodies)", who);
-  if (L.world_size > 1 || L.decomposed || e.nranks() > 1 || e.decomposed())
-    fail("%s: one rank only (no decomposed domain)", who);
+  refuse_decomposed(L, who);
 }
 
 }  // namespace
@@ -321,11 +319,9 @@ bool compute_command(SfLammps& L, const std::vector<std::string>& w)
     const bool per_atom = !c && atom_compute_ncols(L, w[1]) > 0;   // (one ID space: sf_compute_atom.hip holds the others)
     const bool global = !c && !per_atom && global_compute_nvalues(L, w[1]) > 0;   // (sf_global.hip holds those)
     if (!c && !per_atom && !global) fail("Could not find compute ID to delete");   // [3P] Modify::delete_compute
-    if (const char* who = global_uses_compute(L, w[1]))
-      fail("uncompute %s: a %s still uses this compute (%s it first)", w[1].c_str(), who,
-           who[0] == 'f' ? "unfix" : "uncompute");
-    if (ave_histo_uses_compute(L, w[1]))
-      fail("uncompute %s: a fix ave/histo still uses this compute (unfix it first)", w[1].c_str());
+    if (reduce_uses_compute(L, w[1])) fail("uncompute %s: a compute reduce still uses this compute (uncompute it first)", w[1].c_str());
+    if (const char* who = ave_fix_uses_compute(L, w[1]))
+      fail("uncompute %s: a %s still uses this compute (unfix it first)", w[1].c_str(), who);
     if (global) {
       if (thermo_uses_compute(L, w[1]))
         fail("uncompute %s: thermo_style custom still names this compute (give another thermo_style first)", w[1].c_str());
@@ -334,8 +330,6 @@ bool compute_command(SfLammps& L, const std::vector<std::string>& w)
     }
     if (dump_uses_compute(L, w[1]))
       fail("uncompute %s: a dump %s still uses this compute (undump it first)", w[1].c_str(), per_atom ? "custom" : "local");
-    if (ave_chunk_uses_compute(L, w[1]))
-      fail("uncompute %s: a fix ave/chunk still uses this compute (unfix it first)", w[1].c_str());
     if (per_atom) {
       atom_compute_remove(L, w[1]);
       return true;
@@ -492,13 +486,7 @@ long long contact_launches(const SfLammps& L)
 
 }  // namespace sf
 
-namespace {
-sf::SfLammps* handle(void* p)
-{
-  if (!p) sf::fail("null engine handle");
-  return static_cast<sf::SfLammps*>(p);
-}
-}  // namespace
+using sf::handle;
 
 extern "C" {
 

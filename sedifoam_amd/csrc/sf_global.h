@@ -1,7 +1,8 @@
 // sf_global.h -- the global computes `compute ID group reduce MODE input ...`, `compute ID group ke` and `compute ID group
 // erotate/sphere`, and `fix ID group ave/time Nevery Nrepeat Nfreq c_ID ...` (sf_global.hip): one number per step that the
 // user chooses, reduced over the whole bed on the GPU and written as a time series.  The computes share the ID space of the
-// other computes (compute_command of sf_contacts.hip hands the styles over); the fix shares the ID space of fix ave/chunk.
+// other computes (compute_command of sf_contacts.hip hands the styles over); the fix shares the ID space of the other
+// averaging fixes (sf_ave_fix.h).
 #pragma once
 #include <string>
 #include <vector>
@@ -16,8 +17,8 @@ void global_compute_define(SfLammps& L, const std::vector<std::string>& w);
 // the length of global compute `id` (1 for a scalar), whether it is a vector (`c_ID[k]`) and extensive; 0: no such compute
 int global_compute_nvalues(const SfLammps& L, const std::string& id, bool* is_vector = nullptr, bool* extensive = nullptr);
 void global_compute_remove(SfLammps& L, const std::string& id);
-// who names compute `id`: "compute reduce", "fix ave/time", or nullptr
-const char* global_uses_compute(const SfLammps& L, const std::string& id);
+// does a compute reduce name compute `id` as an input?
+bool reduce_uses_compute(const SfLammps& L, const std::string& id);
 // the state changed at an unchanged step: evaluate again when asked next (atom_compute_invalidate calls it)
 void global_invalidate(SfLammps& L);
 // the values of `id` on the state as it stands, on the host (evaluated first when they are stale; one copy, one wait)
@@ -26,17 +27,11 @@ void global_values_host(SfLammps& L, const std::string& id, std::vector<double>*
 // at this address while the compute exists (fix ave/histo bins them there, sf_histo.hip)
 const double* global_values_device(SfLammps& L, const std::string& id);
 
-// ---- the fix ----
+// ---- the fix (its ID space, unfix and the run's cuts: sf_ave_fix.h) ----
 // `fix ID group ave/time ...` from the whole line (its title keywords may be quoted)
 void ave_time_fix_command(SfLammps& L, const std::string& line);
-bool ave_time_fix_exists(const SfLammps& L, const std::string& id);
-// `unfix ID`: false when no fix ave/time has this ID
-bool ave_time_unfix(SfLammps& L, const std::string& id);
 
-// ---- the run (sf::run_steps) ----
-bool ave_time_active(const SfLammps& L);
-// the first step after `step` at which some fix ave/time samples (-1: none)
-long long ave_time_next_step(const SfLammps& L, long long step);
+// ---- the run (ave_fix_step_due of sf_ave_fix.hip) ----
 // One evaluation plan for the engine's current step: the computes of the fix ave/time samples due now and those named in
 // `also` (the c_ columns of a thermo line due now, the global inputs of the fix ave/histo samples due now), each evaluated
 // once; then the samples and outputs of the fixes

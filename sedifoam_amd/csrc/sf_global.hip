@@ -28,12 +28,11 @@
 #include <string>
 #include <vector>
 
-#include <unistd.h>
-
 #include <hip/hip_runtime.h>
 
 #include "../../include/sedifoam_amd.h"
 #include "sf_atom_terms.h"
+#include "sf_ave_fix.h"
 #include "sf_block_reduce.h"
 #include "sf_chunk.h"
 #include "sf_compute_atom.h"
@@ -41,8 +40,6 @@
 #include "sf_gather_col.h"
 #include "sf_global.h"
 #include "sf_global_parse.h"
-#include "sf_handles.h"
-#include "sf_histo.h"
 
 // (a*a + s stays a product and a sum, so that a column's bits do not depend on what the compiler fuses around it)
 #pragma clang fp contract(off)
@@ -207,23 +204,13 @@ struct GlobalCompute {
   bool extensive() const { return kind != G_REDUCE || S.mode == GM_SUM || S.mode == GM_SUMSQ; }
 };
 
-struct AveTimeFix {
+struct AveTimeFix : AveFixState {
   AveTimeSpec S;
-  long long nvalid = 0;
-  int irepeat = 0;
   int slot = -1;   // the accumulator, [nvalues] in the pool
   std::deque<std::vector<double>> blocks;   // ave window: the last M blocks
   std::vector<double> runsum;               // ave running: the sum of all blocks
   long long noutputs = 0;
-  bool have = false;
-  long long out_step = -1;
-  std::vector<double> values;
-  FILE* fp = nullptr;
-  long filepos = 0;
-  ~AveTimeFix()
-  {
-    if (fp) fclose(fp);
-  }
+  std::vector<double> values;   // the latest output
 };
 
 struct GlobalSet {
@@ -246,12 +233,7 @@ struct GlobalSet {
       if (c->id == id) return c.get();
     return nullptr;
   }
-  AveTimeFix* find_fix(const std::string& id)
-  {
-    for (auto& f : fixes)
-      if (f->S.id == id) return f.get();
-    return nullptr;
-  }
+  AveTimeFix* find_fix(const std::string& id) const { return ave_find(fixes, id); }
   void device(hipStream_t st)
   {
     if (pool) return;
@@ -287,13 +269,6 @@ GlobalSet& ensure_set(SfLammps& L)
     L.globals_delete = [](void* p) { delete static_cast<GlobalSet*>(p); };
   }
   return *set_of(L);
-}
-
-void refuse_decomposed(const SfLammps& L, const char* who)
-{
-  const DemEngine& e = L.eng;
-  if (L.world_size > 1 || L.decomposed || e.nranks() > 1 || e.decomposed())
-    fail("%s: one rank only (no decomposed domain)", who);
 }
 
 std::string who_of(const GlobalCompute& c) { return std::string("compute ") + kStyleName[c.kind]; }
@@ -466,8 +441,8 @@ void evaluate(SfLammps& L, GlobalSet& G, const std::vector<GlobalCompute*>& want
         const ReduceInput& in = c->S.inputs[j];
         const GOp op = op_of(c->S.mode);
         pc.ave = c->S.mode == GM_AVE || c->S.mode == GM_AVESQ;
-        if (in.attr != GA_COMPUTE) {
-          pc.col.set(in.attr < GA_VX ? GS_XR : (in.attr < GA_FX ? GS_VM : GS_FORCE), in.attr % 3, op);
+        if (in.attr != AA_COMPUTE) {
+          pc.col.set(in.attr < AA_VX ? GS_XR : (in.attr < AA_FX ? GS_VM : GS_FORCE), in.attr % 3, op);
         } else if (!check_reduce_input(L, in)) {
           int nc = 0;
           const double* val = atom_compute_values(L, in.id, &nc);   // (once per step however many ask)
@@ -543,16 +518,13 @@ void check_fix_value(const SfLammps& L, const AveTimeValue& v)
 
 void write_line(AveTimeFix& F)
 {
-  if (!F.fp) return;
-  if (F.S.overwrite && fseek(F.fp, F.filepos, SEEK_SET) != 0) fail("fix ave/time %s: cannot rewind %s", F.S.id.c_str(), F.S.file.c_str());
-  fprintf(F.fp, "%lld", F.out_step);
-  for (double v : F.values) fprintf(F.fp, F.S.format.c_str(), v);
-  fputc('\n', F.fp);
-  if (fflush(F.fp) != 0) fail("fix ave/time %s: error writing %s", F.S.id.c_str(), F.S.file.c_str());
-  if (F.S.overwrite) {
-    const long end = ftell(F.fp);
-    if (end < 0 || ftruncate(fileno(F.fp), end) != 0) fail("fix ave/time %s: cannot truncate %s", F.S.id.c_str(), F.S.file.c_str());
-  }
+  FILE* fp = F.file.fp();
+  if (!fp) return;
+  fail_if(F.file.begin_block());
+  fprintf(fp, "%lld", F.out_step);
+  for (double v : F.values) fprintf(fp, F.S.format.c_str(), v);
+  fputc('\n', fp);
+  fail_if(F.file.end_block());
 }
 
 // the accumulator of Nrepeat samples -> one output (divided on the host)
@@ -565,8 +537,8 @@ void make_output(SfLammps& L, GlobalSet& G, AveTimeFix& F)
   for (int j = 0; j < nv; j++) block[j] = G.h_buf[j] / nrep;
   F.noutputs++;
   F.values.assign(nv, 0.0);
-  if (F.S.ave == AT_ONE) F.values = block;
-  else if (F.S.ave == AT_RUNNING) {
+  if (F.S.ave == AVE_ONE) F.values = block;
+  else if (F.S.ave == AVE_RUNNING) {
     if (F.runsum.empty()) F.runsum.assign(nv, 0.0);
     for (int j = 0; j < nv; j++) {
       F.runsum[j] += block[j];
@@ -586,18 +558,34 @@ void make_output(SfLammps& L, GlobalSet& G, AveTimeFix& F)
   write_line(F);
 }
 
-long long first_valid(const AveTimeFix& F, long long t0) { return ave_first_valid(t0, F.S.nevery, F.S.nrepeat, F.S.nfreq, F.S.start); }
-
-// a fix whose sample step has passed without a sample (steps taken outside run_steps): begin a new output
-void catch_up(SfLammps& L, GlobalSet& G, AveTimeFix& F)
+bool fix_exists(const SfLammps& L, const std::string& id)
 {
-  const long long step = L.eng.nsteps();
-  if (F.nvalid >= step) return;
-  F.nvalid = first_valid(F, step);
-  if (F.irepeat > 0) {
-    F.irepeat = 0;
-    SF_HIP(hipMemsetAsync(G.pool + F.slot, 0, sizeof(double) * F.S.values.size(), L.eng.stream()));
-  }
+  GlobalSet* G = set_of(L);
+  return G && G->find_fix(id);
+}
+
+bool unfix(SfLammps& L, const std::string& id)
+{
+  GlobalSet* G = set_of(L);
+  const std::unique_ptr<AveTimeFix> f = G ? ave_take(L, G->fixes, id) : nullptr;
+  if (f) G->give(f->slot, (int)f->S.values.size());
+  return f != nullptr;
+}
+
+bool fix_uses_compute(const SfLammps& L, const std::string& id)
+{
+  const GlobalSet* G = set_of(L);
+  if (!G) return false;
+  for (const auto& f : G->fixes)
+    for (const AveTimeValue& v : f->S.values)
+      if (v.id == id) return true;
+  return false;
+}
+
+long long next_step(const SfLammps& L, long long step)
+{
+  const GlobalSet* G = set_of(L);
+  return G ? ave_next(G->fixes, step) : -1;
 }
 
 GlobalCompute& compute_of(GlobalSet& G, const std::string& id, const char* missing)
@@ -608,6 +596,12 @@ GlobalCompute& compute_of(GlobalSet& G, const std::string& id, const char* missi
 }
 
 }  // namespace
+
+const AveFixKind& ave_time_kind()
+{
+  static const AveFixKind kind = {"fix ave/time", fix_exists, unfix, fix_uses_compute, next_step};
+  return kind;
+}
 
 // ---- the computes ----
 
@@ -629,10 +623,9 @@ void global_compute_define(SfLammps& L, const std::vector<std::string>& w)
     if (w[3] == kStyleName[k]) c->kind = (GKind)k;
   refuse_decomposed(L, who_of(*c).c_str());
   if (c->kind == G_REDUCE) {
-    const std::string err = parse_reduce(w, &c->S);
-    if (!err.empty()) fail("%s", err.c_str());
+    fail_if(parse_reduce(w, &c->S));
     for (const ReduceInput& in : c->S.inputs)
-      if (in.attr == GA_COMPUTE) check_reduce_input(L, in);
+      if (in.attr == AA_COMPUTE) check_reduce_input(L, in);
     c->nvalues = (int)c->S.inputs.size();
   } else if (w.size() != 4)
     fail("Illegal compute %s command", w[3].c_str());
@@ -664,18 +657,15 @@ void global_compute_remove(SfLammps& L, const std::string& id)
     }
 }
 
-const char* global_uses_compute(const SfLammps& L, const std::string& id)
+bool reduce_uses_compute(const SfLammps& L, const std::string& id)
 {
   const GlobalSet* G = set_of(L);
-  if (!G) return nullptr;
+  if (!G) return false;
   for (const auto& c : G->computes)
     if (c->kind == G_REDUCE)
       for (const ReduceInput& in : c->S.inputs)
-        if (in.attr == GA_COMPUTE && in.id == id) return "compute reduce";
-  for (const auto& f : G->fixes)
-    for (const AveTimeValue& v : f->S.values)
-      if (v.id == id) return "fix ave/time";
-  return nullptr;
+        if (in.attr == AA_COMPUTE && in.id == id) return true;
+  return false;
 }
 
 void global_invalidate(SfLammps& L)
@@ -711,69 +701,23 @@ void ave_time_fix_command(SfLammps& L, const std::string& line)
   const std::string qerr = split_quoted(line, &w);
   if (!qerr.empty()) fail("%s", qerr.c_str());
   auto F = std::make_unique<AveTimeFix>();
-  const std::string err = parse_ave_time(w, &F->S);
-  if (!err.empty()) fail("%s", err.c_str());
+  fail_if(parse_ave_time(w, &F->S));
   refuse_decomposed(L, "fix ave/time");
   (void)L.eng.group_bit(F->S.group);   // (the group must exist; it is not used, as in LAMMPS)
   GlobalSet& G = ensure_set(L);
-  if (G.find_fix(F->S.id) || ave_chunk_fix_exists(L, F->S.id) || ave_histo_fix_exists(L, F->S.id))
+  if (ave_fix_exists(L, F->S.id))
     fail("fix ave/time %s: this fix ID is in use (unfix it first)", F->S.id.c_str());
   for (const AveTimeValue& v : F->S.values) check_fix_value(L, v);
   hipStream_t st = L.eng.stream();
   G.device(st);
   const int nv = (int)F->S.values.size();
-  F->nvalid = first_valid(*F, L.eng.nsteps());
-  if (!F->S.file.empty()) {
-    F->fp = fopen(F->S.file.c_str(), "w+");
-    if (!F->fp) fail("Cannot open fix ave/time file %s", F->S.file.c_str());
-    std::string t2 = "# TimeStep";
-    for (const AveTimeValue& v : F->S.values) t2 += " " + v.word;
-    const std::string t1 = "# Time-averaged data for fix " + F->S.id;
-    fprintf(F->fp, "%s\n%s\n", (F->S.has_title[0] ? F->S.title[0] : t1).c_str(), (F->S.has_title[1] ? F->S.title[1] : t2).c_str());
-    fflush(F->fp);
-    F->filepos = ftell(F->fp);
-  }
+  F->S.begin(L.eng.nsteps());
+  std::string titles[2] = {"# Time-averaged data for fix " + F->S.id, "# TimeStep"};
+  for (const AveTimeValue& v : F->S.values) titles[1] += " " + v.word;
+  fail_if(F->file.open(F->S, "ave/time", F->S.id, titles, 2));
   F->slot = G.take(nv);
   SF_HIP(hipMemsetAsync(G.pool + F->slot, 0, sizeof(double) * (size_t)nv, st));
   G.fixes.push_back(std::move(F));
-}
-
-bool ave_time_fix_exists(const SfLammps& L, const std::string& id)
-{
-  GlobalSet* G = set_of(L);
-  return G && G->find_fix(id);
-}
-
-bool ave_time_unfix(SfLammps& L, const std::string& id)
-{
-  GlobalSet* G = set_of(L);
-  if (!G) return false;
-  for (size_t k = 0; k < G->fixes.size(); k++)
-    if (G->fixes[k]->S.id == id) {
-      SF_HIP(hipStreamSynchronize(L.eng.stream()));   // (a sample queued on the stream may still add into its accumulator)
-      G->give(G->fixes[k]->slot, (int)G->fixes[k]->S.values.size());
-      G->fixes.erase(G->fixes.begin() + k);   // (closes its file)
-      return true;
-    }
-  return false;
-}
-
-bool ave_time_active(const SfLammps& L)
-{
-  const GlobalSet* G = set_of(L);
-  return G && !G->fixes.empty();
-}
-
-long long ave_time_next_step(const SfLammps& L, long long step)
-{
-  const GlobalSet* G = set_of(L);
-  long long best = -1;
-  if (!G) return best;
-  for (const auto& f : G->fixes) {
-    const long long nx = f->nvalid > step ? f->nvalid : first_valid(*f, step + 1);
-    if (best < 0 || nx < best) best = nx;
-  }
-  return best;
 }
 
 void global_step_due(SfLammps& L, const std::vector<std::string>& also)
@@ -783,8 +727,9 @@ void global_step_due(SfLammps& L, const std::vector<std::string>& also)
   const long long step = L.eng.nsteps();
   std::vector<AveTimeFix*> due;
   for (auto& f : G->fixes) {
-    catch_up(L, *G, *f);
-    if (f->nvalid == step) due.push_back(f.get());
+    if (f->S.catch_up(step))   // (the samples of the output that was under way are dropped)
+      SF_HIP(hipMemsetAsync(G->pool + f->slot, 0, sizeof(double) * f->S.values.size(), L.eng.stream()));
+    if (f->S.due(step)) due.push_back(f.get());
   }
   if (due.empty() && also.empty()) return;
   if (!due.empty()) refuse_decomposed(L, "fix ave/time");
@@ -800,27 +745,13 @@ void global_step_due(SfLammps& L, const std::vector<std::string>& also)
     }
   for (const std::string& id : also) want.push_back(&compute_of(*G, id, "Could not find thermo custom compute ID"));
   evaluate(L, *G, want, accs);
-  for (AveTimeFix* f : due) {
-    f->irepeat++;
-    if (f->irepeat < f->S.nrepeat) {
-      f->nvalid = step + f->S.nevery;
-      continue;
-    }
-    f->irepeat = 0;
-    f->nvalid = step + f->S.nfreq - (f->S.nrepeat - 1) * f->S.nevery;
-    make_output(L, *G, *f);
-  }
+  for (AveTimeFix* f : due)
+    if (f->S.sampled(step)) make_output(L, *G, *f);
 }
 
 }  // namespace sf
 
-namespace {
-sf::SfLammps* handle(void* p)
-{
-  if (!p) sf::fail("null engine handle");
-  return static_cast<sf::SfLammps*>(p);
-}
-}  // namespace
+using sf::handle;
 
 extern "C" {
 
@@ -902,26 +833,10 @@ int sf_lammps_global_cost(void* ptr, const char* id, double* ms)
   sf::GlobalSet* G = sf::set_of(L);
   sf::GlobalCompute* c = G ? G->find(id) : nullptr;
   if (!c) sf::fail("Could not find compute ID %s", id);
-  hipStream_t st = L.eng.stream();
-  hipEvent_t ev[2];
-  for (hipEvent_t& e : ev) SF_HIP(hipEventCreate(&e));
-  struct EvGuard {
-    hipEvent_t* ev;
-    ~EvGuard()
-    {
-      for (int k = 0; k < 2; k++) (void)hipEventDestroy(ev[k]);
-    }
-  } guard{ev};
   // (the per-atom computes behind c_ inputs are evaluated outside the time: sf_lammps_compute_atom_cost times them)
   sf::evaluate(L, *G, {c}, {});
   c->step = -1;
-  SF_HIP(hipEventRecord(ev[0], st));
-  sf::evaluate(L, *G, {c}, {});
-  SF_HIP(hipEventRecord(ev[1], st));
-  SF_HIP(hipStreamSynchronize(st));
-  float t = 0.f;
-  SF_HIP(hipEventElapsedTime(&t, ev[0], ev[1]));
-  *ms = (double)t;
+  *ms = sf::stream_ms(L.eng.stream(), [&] { sf::evaluate(L, *G, {c}, {}); });
   SF_API_END(0)
 }
 

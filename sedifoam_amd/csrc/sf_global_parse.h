@@ -2,9 +2,9 @@
 // `fix ID group ave/time Nevery Nrepeat Nfreq value ... keywords` and a `c_ID` / `c_ID[k]` column of thermo_style custom
 // ([3P] LAMMPS names and rules: ComputeReduce::ComputeReduce, ComputePropertyAtom, FixAveTime::FixAveTime / options /
 // nextvalid, Thermo::parse_fields), on the host with nothing but the standard library, so that this code can be compiled
-// into a stand-alone program and run under the host sanitizers (sf_chunk_parse.h is the precedent, and holds the shared
-// pieces: split_quoted, chunk_parse_int, ave_format_ok, ave_first_valid).  Every parser returns an empty string, or the
-// error text.
+// into a stand-alone program and run under the host sanitizers (sf_chunk_parse.h is the precedent, and holds split_quoted
+// and ave_format_ok; the schedule, the file, ave and start keywords, the attribute words and parse_cref are those of
+// sf_ave_common.h).  Every parser returns an empty string, or the error text.
 #pragma once
 #include <cstdlib>
 #include <cstring>
@@ -15,37 +15,16 @@
 
 namespace sf {
 
-// `word` = c_ID or c_ID[k] (the caller has seen the "c_"): the ID and k >= 1 (0: no index given).  false: malformed
-inline bool global_parse_cref(const std::string& word, std::string* id, long* index)
-{
-  if (word.size() < 3 || word.compare(0, 2, "c_") != 0) return false;
-  *id = word.substr(2);
-  *index = 0;
-  const size_t br = id->find('[');
-  if (br != std::string::npos) {
-    const char* first = id->c_str() + br + 1;
-    if (*first < '0' || *first > '9') return false;   // (no sign, no blank)
-    char* end = nullptr;
-    const long k = std::strtol(first, &end, 10);
-    if (end == first || *end != ']' || end[1] || k < 1 || k > 1000000) return false;
-    *index = k;
-    id->resize(br);
-  }
-  if (id->empty() || id->find(']') != std::string::npos) return false;
-  return true;
-}
-
 // ---- compute reduce ----
 
 enum GlobalMode { GM_SUM, GM_MIN, GM_MAX, GM_AVE, GM_SUMSQ, GM_AVESQ };
-enum GlobalAttr { GA_X, GA_Y, GA_Z, GA_VX, GA_VY, GA_VZ, GA_FX, GA_FY, GA_FZ, GA_COMPUTE };
 constexpr int kReduceMaxInputs = 64;
 
 struct ReduceInput {
-  int attr = GA_X;
+  int attr = AA_X;
   std::string word;   // as typed
-  std::string id;     // GA_COMPUTE
-  long index = 0;     // GA_COMPUTE: k of c_ID[k], 0: none
+  std::string id;     // AA_COMPUTE
+  long index = 0;     // AA_COMPUTE: k of c_ID[k], 0: none
 };
 
 struct ReduceSpec {
@@ -70,22 +49,19 @@ inline std::string parse_reduce(const std::vector<std::string>& w, ReduceSpec* o
     return "compute reduce: mode " + w[4] + " is not supported (sum, min, max, ave, sumsq and avesq are)";
   if (mode < 0) return illegal;
   S.mode = mode;
-  static const char* const plain[9] = {"x", "y", "z", "vx", "vy", "vz", "fx", "fy", "fz"};
   for (size_t k = 5; k < w.size(); k++) {
     const std::string& s = w[k];
     ReduceInput in;
     in.word = s;
-    int a = -1;
-    for (int q = 0; q < 9; q++)
-      if (s == plain[q]) a = q;
+    const int a = ave_attr_of(s);
     if (a >= 0) in.attr = a;
     else if (s == "replace" || s == "inputs")
       return "compute reduce: keyword " + s + " is not supported";
     else if (s.compare(0, 2, "f_") == 0 || s.compare(0, 2, "v_") == 0)
       return "compute reduce: " + s + " is not supported (f_ and v_ inputs are not; x y z vx vy vz fx fy fz, c_ID and c_ID[k] are)";
     else if (s.compare(0, 2, "c_") == 0) {
-      in.attr = GA_COMPUTE;
-      if (!global_parse_cref(s, &in.id, &in.index)) return illegal;
+      in.attr = AA_COMPUTE;
+      if (!parse_cref(s, &in.id, &in.index)) return illegal;
     } else
       return illegal;
     if ((int)S.inputs.size() >= kReduceMaxInputs) return "compute reduce: more than 64 inputs";
@@ -129,24 +105,17 @@ inline std::string parse_property_atom(const std::vector<std::string>& w, std::v
 // ---- fix ave/time ----
 
 constexpr int kAveTimeMaxValues = 64;
-enum AveTimeMode { AT_ONE, AT_RUNNING, AT_WINDOW };
 
 struct AveTimeValue {
   std::string word, id;
   long index = 0;
 };
 
-struct AveTimeSpec {
+struct AveTimeSpec : AveSchedule, AveFileSpec {   // (title3 belongs to mode vector: accepted and unused)
   std::string id, group;
-  long nevery = 1, nrepeat = 1, nfreq = 1;
   std::vector<AveTimeValue> values;
-  int ave = AT_ONE;
+  int ave = AVE_ONE;
   long window = 0;
-  long start = 0;
-  std::string file;
-  bool overwrite = false;
-  bool has_title[2] = {false, false};
-  std::string title[2];
   std::string format = " %g";
 };
 
@@ -166,9 +135,7 @@ inline std::string parse_ave_time(const std::vector<std::string>& w, AveTimeSpec
   AveTimeSpec S;
   S.id = w[1];
   S.group = w[2];
-  if (!chunk_parse_int(w[4], &S.nevery) || !chunk_parse_int(w[5], &S.nrepeat) || !chunk_parse_int(w[6], &S.nfreq)) return illegal;
-  if (S.nevery <= 0 || S.nrepeat <= 0 || S.nfreq <= 0) return illegal;
-  if (S.nfreq % S.nevery || S.nrepeat * S.nevery > S.nfreq) return illegal;
+  if (!S.parse(w, 4, illegal).empty()) return illegal;
   size_t k = 7;
   for (; k < w.size(); k++) {
     const std::string& s = w[k];
@@ -177,7 +144,7 @@ inline std::string parse_ave_time(const std::vector<std::string>& w, AveTimeSpec
     if (s.compare(0, 2, "c_") != 0) break;
     AveTimeValue v;
     v.word = s;
-    if (!global_parse_cref(s, &v.id, &v.index)) return illegal;
+    if (!parse_cref(s, &v.id, &v.index)) return illegal;
     if ((int)S.values.size() >= kAveTimeMaxValues) return "fix ave/time: more than 64 values";
     S.values.push_back(v);
   }
@@ -185,41 +152,17 @@ inline std::string parse_ave_time(const std::vector<std::string>& w, AveTimeSpec
   while (k < w.size()) {
     const std::string& key = w[k];
     const size_t left = w.size() - k - 1;
-    if (key == "ave") {
-      if (left < 1) return illegal;
-      if (w[k + 1] == "one") S.ave = AT_ONE, k += 2;
-      else if (w[k + 1] == "running") S.ave = AT_RUNNING, k += 2;
-      else if (w[k + 1] == "window") {
-        if (left < 2 || !chunk_parse_int(w[k + 2], &S.window) || S.window <= 0 || S.window > 100000) return illegal;
-        S.ave = AT_WINDOW;
-        k += 3;
-      } else
-        return illegal;
-    } else if (key == "start") {
-      if (left < 1 || !chunk_parse_int(w[k + 1], &S.start) || S.start < 0) return illegal;
-      k += 2;
-    } else if (key == "mode") {
+    AveKey shared = ave_file_keyword(w, &k, &S);
+    if (shared == AK_NOT_MINE) shared = ave_mode_keyword(w, &k, &S.ave, &S.window, &S.start);
+    if (shared == AK_ERROR) return illegal;
+    if (shared == AK_CONSUMED) continue;
+    if (key == "mode") {
       if (left < 1) return illegal;
       if (w[k + 1] == "vector") return "fix ave/time: mode vector is not supported (mode scalar is)";
       if (w[k + 1] != "scalar") return illegal;
       k += 2;
     } else if (key == "off") {
       return "fix ave/time: off is not supported (it belongs to mode vector, which is not)";
-    } else if (key == "file") {
-      if (left < 1 || w[k + 1].empty()) return illegal;
-      S.file = w[k + 1];
-      k += 2;
-    } else if (key == "overwrite") {
-      S.overwrite = true;
-      k += 1;
-    } else if (key == "title1" || key == "title2" || key == "title3") {
-      if (left < 1) return illegal;
-      const int t = key[5] - '1';
-      if (t < 2) {   // (title3 belongs to mode vector: accepted and unused)
-        S.has_title[t] = true;
-        S.title[t] = w[k + 1];
-      }
-      k += 2;
     } else if (key == "format") {
       if (left < 1) return illegal;
       if (!ave_time_format_ok(w[k + 1]))
@@ -237,7 +180,7 @@ inline std::string parse_ave_time(const std::vector<std::string>& w, AveTimeSpec
 
 inline std::string parse_thermo_column(const std::string& word, std::string* id, long* index)
 {
-  if (!global_parse_cref(word, id, index)) return "Invalid keyword in thermo_style custom command: " + word;
+  if (!parse_cref(word, id, index)) return "Invalid keyword in thermo_style custom command: " + word;
   return std::string();
 }
 

@@ -1,4 +1,5 @@
-// sf_handles.h -- what the opaque `void* ptr` of the sf_lammps_* / sf_dem_* C-ABI points to.
+// sf_handles.h -- what the opaque `void* ptr` of the sf_lammps_* / sf_dem_* C-ABI points to, and the small helpers every
+// file behind that ABI needs: handle(), refuse_decomposed(), stream_ms().
 #pragma once
 #include <cstdint>
 #include <string>
@@ -63,4 +64,40 @@ struct SfLammps {
     if (halo && halo_delete) halo_delete(halo);
   }
 };
+
+inline SfLammps* handle(void* p)
+{
+  if (!p) fail("null engine handle");
+  return static_cast<SfLammps*>(p);
+}
+
+// the GPU milliseconds of what `work` puts on stream `s`, between two events (waits for the stream)
+template <class Work>
+double stream_ms(hipStream_t s, Work&& work)
+{
+  struct Events {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ~Events()
+    {
+      for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    }
+  } E;
+  for (hipEvent_t& e : E.ev) SF_HIP(hipEventCreate(&e));
+  SF_HIP(hipEventRecord(E.ev[0], s));
+  work();
+  SF_HIP(hipEventRecord(E.ev[1], s));
+  SF_HIP(hipStreamSynchronize(s));
+  float ms = 0.f;
+  SF_HIP(hipEventElapsedTime(&ms, E.ev[0], E.ev[1]));
+  return (double)ms;
+}
+
+// what reads the whole bed from one device refuses a decomposed run; `who` as in "fix ave/chunk"
+inline void refuse_decomposed(const SfLammps& L, const char* who)
+{
+  const DemEngine& e = L.eng;
+  if (L.world_size > 1 || L.decomposed || e.nranks() > 1 || e.decomposed())
+    fail("%s: one rank only (no decomposed domain)", who);
+}
 }  // namespace sf

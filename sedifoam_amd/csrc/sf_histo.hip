@@ -25,17 +25,14 @@
 #include <string>
 #include <vector>
 
-#include <unistd.h>
-
 #include <hip/hip_runtime.h>
 
 #include "../../include/sedifoam_amd.h"
-#include "sf_chunk.h"
+#include "sf_ave_fix.h"
 #include "sf_compute_atom.h"
 #include "sf_contacts.h"
 #include "sf_gather_col.h"
 #include "sf_global.h"
-#include "sf_handles.h"
 #include "sf_histo.h"
 
 // ((v - lo) * bininv stays a difference and a product, whatever the compiler would fuse around it: the bin of a value is
@@ -156,24 +153,17 @@ __global__ __launch_bounds__(kHBlock) void k_histo_bin(GRecords R, HTable T, His
 
 // ---- host side ----
 
-struct HistoFix {
+struct HistoFix : AveFixState {
   HistoSpec S;
   HistoBins B;
   int kind = HK_PERATOM;
   int groupbit = 1;
-  long long nvalid = 0;
-  int irepeat = 0;
   unsigned long long* acc = nullptr;   // device [nbins + kHExtra]
   HistoAverager A;
-  bool have = false;
-  long long out_step = -1;
-  HistoBlock out;
-  FILE* fp = nullptr;
-  long filepos = 0;
+  HistoBlock out;   // the latest output
   size_t nacc() const { return (size_t)B.nbins + kHExtra; }
   ~HistoFix()
   {
-    if (fp) fclose(fp);
     if (acc) (void)hipFree(acc);
   }
 };
@@ -189,12 +179,7 @@ struct HistoSet {
     if (h_buf) (void)hipHostFree(h_buf);
     if (cost_acc) (void)hipFree(cost_acc);
   }
-  HistoFix* find_fix(const std::string& id)
-  {
-    for (auto& f : fixes)
-      if (f->S.id == id) return f.get();
-    return nullptr;
-  }
+  HistoFix* find_fix(const std::string& id) const { return ave_find(fixes, id); }
   void device()
   {
     if (h_buf) return;
@@ -213,20 +198,13 @@ HistoSet& ensure_set(SfLammps& L)
   return *set_of(L);
 }
 
-void refuse_decomposed(const SfLammps& L)
-{
-  const DemEngine& e = L.eng;
-  if (L.world_size > 1 || L.decomposed || e.nranks() > 1 || e.decomposed())
-    fail("fix ave/histo: one rank only (no decomposed domain)");
-}
-
 // The kind of the values and every rule that needs the computes: checked at the fix line and again at every sample (a
 // compute may have been removed and defined anew)
 int check_values(const SfLammps& L, const HistoSpec& S)
 {
   std::vector<int> kinds;
   for (const HistoValue& v : S.values) {
-    if (v.attr != HA_COMPUTE) kinds.push_back(HK_PERATOM);
+    if (v.attr != AA_COMPUTE) kinds.push_back(HK_PERATOM);
     else if (atom_compute_ncols(L, v.id) > 0) kinds.push_back(HK_PERATOM);
     else if (pair_local_exists(L, v.id)) kinds.push_back(HK_LOCAL);
     else if (global_compute_nvalues(L, v.id) > 0) kinds.push_back(HK_GLOBAL);
@@ -241,7 +219,7 @@ int check_values(const SfLammps& L, const HistoSpec& S)
   if (kind == HK_PERATOM && S.mode == HM_SCALAR) fail("Fix ave/histo cannot input per-atom values in scalar mode");
   if (kind == HK_LOCAL && S.mode == HM_SCALAR) fail("Fix ave/histo cannot input local values in scalar mode");
   for (const HistoValue& v : S.values) {
-    if (v.attr != HA_COMPUTE) continue;
+    if (v.attr != AA_COMPUTE) continue;
     if (kind == HK_PERATOM) {
       const int nc = atom_compute_ncols(L, v.id);
       if (v.index == 0 && nc != 1) fail("Fix ave/histo compute does not calculate a per-atom vector");
@@ -318,7 +296,7 @@ long long build_table(SfLammps& L, const HistoFix& F, const std::vector<int>& wh
     int lim = 0;
     if (F.kind == HK_PERATOM) {
       c.groupbit = F.groupbit;
-      if (v.attr != HA_COMPUTE) c.set(v.attr < HA_VX ? GS_XR : (v.attr < HA_FX ? GS_VM : GS_FORCE), v.attr % 3, 0);
+      if (v.attr != AA_COMPUTE) c.set(v.attr < AA_VX ? GS_XR : (v.attr < AA_FX ? GS_VM : GS_FORCE), v.attr % 3, 0);
       else {
         int nc = 0;
         const double* val = atom_compute_values(L, v.id, &nc);   // (once per step however many ask)
@@ -371,7 +349,7 @@ void launch_table(SfLammps& L, HistoSet& H, const HistoFix& F, const HTable& T, 
 
 void sample(SfLammps& L, HistoSet& H, HistoFix& F)
 {
-  refuse_decomposed(L);
+  refuse_decomposed(L, "fix ave/histo");
   F.kind = check_values(L, F.S);
   for (const std::vector<int>& which : launch_groups(F)) {
     HTable T;
@@ -382,20 +360,16 @@ void sample(SfLammps& L, HistoSet& H, HistoFix& F)
 
 void write_block(HistoFix& F)
 {
-  if (!F.fp) return;
-  const char* id = F.S.id.c_str();
-  if (F.S.overwrite && fseek(F.fp, F.filepos, SEEK_SET) != 0) fail("fix ave/histo %s: cannot rewind %s", id, F.S.file.c_str());
+  FILE* fp = F.file.fp();
+  if (!fp) return;
+  fail_if(F.file.begin_block());
   const HistoBlock& o = F.out;
-  fprintf(F.fp, "%lld %d %g %g %g %g\n", F.out_step, F.B.nbins, o.total, o.missing, o.min, o.max);
+  fprintf(fp, "%lld %d %g %g %g %g\n", F.out_step, F.B.nbins, o.total, o.missing, o.min, o.max);
   for (int i = 0; i < F.B.nbins; i++) {
-    if (o.total > 0.0) fprintf(F.fp, "%d %g %g %g\n", i + 1, histo_coord(F.B, i), o.count[i], o.count[i] / o.total);
-    else fprintf(F.fp, "%d %g 0 0\n", i + 1, histo_coord(F.B, i));
+    if (o.total > 0.0) fprintf(fp, "%d %g %g %g\n", i + 1, histo_coord(F.B, i), o.count[i], o.count[i] / o.total);
+    else fprintf(fp, "%d %g 0 0\n", i + 1, histo_coord(F.B, i));
   }
-  if (fflush(F.fp) != 0) fail("fix ave/histo %s: error writing %s", id, F.S.file.c_str());
-  if (F.S.overwrite) {
-    const long end = ftell(F.fp);
-    if (end < 0 || ftruncate(fileno(F.fp), end) != 0) fail("fix ave/histo %s: cannot truncate %s", id, F.S.file.c_str());
-  }
+  fail_if(F.file.end_block());
 }
 
 // the counters of Nrepeat samples -> one output: one copy to pinned memory, zeroed on the stream, one wait
@@ -421,21 +395,50 @@ void make_output(SfLammps& L, HistoSet& H, HistoFix& F)
   write_block(F);
 }
 
-long long first_valid(const HistoFix& F, long long t0) { return ave_first_valid(t0, F.S.nevery, F.S.nrepeat, F.S.nfreq, F.S.start); }
-
-// a fix whose sample step has passed without a sample (steps taken outside run_steps): begin a new output
-void catch_up(SfLammps& L, HistoFix& F)
+// a fix whose sample step has passed without a sample (steps taken outside run_steps) begins a new output, without the
+// samples of the one that was under way.  Is a sample of F due at the engine's step?
+bool due_now(SfLammps& L, HistoFix& F)
 {
   const long long step = L.eng.nsteps();
-  if (F.nvalid >= step) return;
-  F.nvalid = first_valid(F, step);
-  if (F.irepeat > 0) {
-    F.irepeat = 0;
-    SF_HIP(hipMemsetAsync(F.acc, 0, sizeof(unsigned long long) * F.nacc(), L.eng.stream()));
-  }
+  if (F.S.catch_up(step)) SF_HIP(hipMemsetAsync(F.acc, 0, sizeof(unsigned long long) * F.nacc(), L.eng.stream()));
+  return F.S.due(step);
+}
+
+bool fix_exists(const SfLammps& L, const std::string& id)
+{
+  HistoSet* H = set_of(L);
+  return H && H->find_fix(id);
+}
+
+bool unfix(SfLammps& L, const std::string& id)
+{
+  HistoSet* H = set_of(L);
+  return H && ave_take(L, H->fixes, id);
+}
+
+bool uses_compute(const SfLammps& L, const std::string& id)
+{
+  const HistoSet* H = set_of(L);
+  if (!H) return false;
+  for (const auto& f : H->fixes)
+    for (const HistoValue& v : f->S.values)
+      if (v.attr == AA_COMPUTE && v.id == id) return true;
+  return false;
+}
+
+long long next_step(const SfLammps& L, long long step)
+{
+  const HistoSet* H = set_of(L);
+  return H ? ave_next(H->fixes, step) : -1;
 }
 
 }  // namespace
+
+const AveFixKind& ave_histo_kind()
+{
+  static const AveFixKind kind = {"fix ave/histo", fix_exists, unfix, uses_compute, next_step};
+  return kind;
+}
 
 void ave_histo_fix_command(SfLammps& L, const std::string& line)
 {
@@ -443,90 +446,34 @@ void ave_histo_fix_command(SfLammps& L, const std::string& line)
   const std::string qerr = split_quoted(line, &w);
   if (!qerr.empty()) fail("%s", qerr.c_str());
   auto F = std::make_unique<HistoFix>();
-  const std::string err = parse_ave_histo(w, &F->S);
-  if (!err.empty()) fail("%s", err.c_str());
-  refuse_decomposed(L);
+  fail_if(parse_ave_histo(w, &F->S));
+  refuse_decomposed(L, "fix ave/histo");
   F->groupbit = L.eng.group_bit(F->S.group);
   HistoSet& H = ensure_set(L);
-  if (H.find_fix(F->S.id) || ave_time_fix_exists(L, F->S.id) || ave_chunk_fix_exists(L, F->S.id))
+  if (ave_fix_exists(L, F->S.id))
     fail("fix ave/histo %s: this fix ID is in use (unfix it first)", F->S.id.c_str());
   F->kind = check_values(L, F->S);
   F->B = histo_bins(F->S.lo, F->S.hi, F->S.nbin, F->S.beyond);
   F->A.ave = F->S.ave;
   F->A.window = F->S.window;
-  F->nvalid = first_valid(*F, L.eng.nsteps());
+  F->S.begin(L.eng.nsteps());
   H.device();
-  if (!F->S.file.empty()) {
-    F->fp = fopen(F->S.file.c_str(), "w+");
-    if (!F->fp) fail("Cannot open fix ave/histo file %s", F->S.file.c_str());
-    const std::string t[3] = {"# Histogrammed data for fix " + F->S.id,
-                              "# TimeStep Number-of-bins Total-counts Missing-counts Min-value Max-value",
-                              "# Bin Coord Count Count/Total"};
-    for (int k = 0; k < 3; k++) fprintf(F->fp, "%s\n", (F->S.has_title[k] ? F->S.title[k] : t[k]).c_str());
-    fflush(F->fp);
-    F->filepos = ftell(F->fp);
-  }
+  const std::string titles[3] = {"# Histogrammed data for fix " + F->S.id,
+                                 "# TimeStep Number-of-bins Total-counts Missing-counts Min-value Max-value",
+                                 "# Bin Coord Count Count/Total"};
+  fail_if(F->file.open(F->S, "ave/histo", F->S.id, titles, 3));
   SF_HIP(hipMalloc(&F->acc, sizeof(unsigned long long) * F->nacc()));
   SF_HIP(hipMemsetAsync(F->acc, 0, sizeof(unsigned long long) * F->nacc(), L.eng.stream()));
   H.fixes.push_back(std::move(F));
-}
-
-bool ave_histo_fix_exists(const SfLammps& L, const std::string& id)
-{
-  HistoSet* H = set_of(L);
-  return H && H->find_fix(id);
-}
-
-bool ave_histo_unfix(SfLammps& L, const std::string& id)
-{
-  HistoSet* H = set_of(L);
-  if (!H) return false;
-  for (size_t k = 0; k < H->fixes.size(); k++)
-    if (H->fixes[k]->S.id == id) {
-      SF_HIP(hipStreamSynchronize(L.eng.stream()));   // (a sample queued on the stream may still add into its counters)
-      H->fixes.erase(H->fixes.begin() + k);   // (closes its file)
-      return true;
-    }
-  return false;
-}
-
-bool ave_histo_uses_compute(const SfLammps& L, const std::string& id)
-{
-  const HistoSet* H = set_of(L);
-  if (!H) return false;
-  for (const auto& f : H->fixes)
-    for (const HistoValue& v : f->S.values)
-      if (v.attr == HA_COMPUTE && v.id == id) return true;
-  return false;
-}
-
-bool ave_histo_active(const SfLammps& L)
-{
-  const HistoSet* H = set_of(L);
-  return H && !H->fixes.empty();
-}
-
-long long ave_histo_next_step(const SfLammps& L, long long step)
-{
-  const HistoSet* H = set_of(L);
-  long long best = -1;
-  if (!H) return best;
-  for (const auto& f : H->fixes) {
-    const long long nx = f->nvalid > step ? f->nvalid : first_valid(*f, step + 1);
-    if (best < 0 || nx < best) best = nx;
-  }
-  return best;
 }
 
 void ave_histo_global_ids_due(SfLammps& L, std::vector<std::string>* ids)
 {
   HistoSet* H = set_of(L);
   if (!H) return;
-  const long long step = L.eng.nsteps();
   for (auto& f : H->fixes) {
-    catch_up(L, *f);
-    if (f->nvalid != step || f->kind != HK_GLOBAL) continue;
-    refuse_decomposed(L);
+    if (!due_now(L, *f) || f->kind != HK_GLOBAL) continue;
+    refuse_decomposed(L, "fix ave/histo");
     f->kind = check_values(L, f->S);
     if (f->kind != HK_GLOBAL) continue;
     for (const HistoValue& v : f->S.values)
@@ -538,31 +485,18 @@ void ave_histo_sample_due(SfLammps& L)
 {
   HistoSet* H = set_of(L);
   if (!H) return;
-  const long long step = L.eng.nsteps();
-  for (auto& fp : H->fixes) {
-    HistoFix& f = *fp;
-    catch_up(L, f);
-    if (f.nvalid != step) continue;
-    sample(L, *H, f);
-    f.irepeat++;
-    if (f.irepeat < f.S.nrepeat) {
-      f.nvalid = step + f.S.nevery;
-      continue;
-    }
-    f.irepeat = 0;
-    f.nvalid = step + f.S.nfreq - (f.S.nrepeat - 1) * f.S.nevery;
-    make_output(L, *H, f);
+  for (auto& f : H->fixes) {
+    if (!due_now(L, *f)) continue;
+    sample(L, *H, *f);
+    if (f->S.sampled(L.eng.nsteps())) make_output(L, *H, *f);
   }
 }
 
 }  // namespace sf
 
+using sf::handle;
+
 namespace {
-sf::SfLammps* handle(void* p)
-{
-  if (!p) sf::fail("null engine handle");
-  return static_cast<sf::SfLammps*>(p);
-}
 sf::HistoFix& fix_of(void* ptr, const char* id)
 {
   sf::HistoSet* H = sf::set_of(*handle(ptr));
@@ -615,18 +549,9 @@ int sf_lammps_ave_histo_cost(void* ptr, const char* id, double* ms)
   if (!id || !ms) sf::fail("sf_lammps_ave_histo_cost: null argument");
   sf::HistoFix& F = fix_of(ptr, id);
   sf::HistoSet& H = *sf::set_of(L);
-  sf::refuse_decomposed(L);
+  sf::refuse_decomposed(L, "fix ave/histo");
   F.kind = sf::check_values(L, F.S);
   hipStream_t st = L.eng.stream();
-  hipEvent_t ev[2];
-  for (hipEvent_t& e : ev) SF_HIP(hipEventCreate(&e));
-  struct EvGuard {
-    hipEvent_t* ev;
-    ~EvGuard()
-    {
-      for (int k = 0; k < 2; k++) (void)hipEventDestroy(ev[k]);
-    }
-  } guard{ev};
   // (the counts go into a buffer of the set: the fix's counters are untouched.  What the columns read -- per-atom computes,
   // contact rows, global computes -- is evaluated outside the time: each has a cost query of its own)
   SF_HIP(hipMemsetAsync(H.cost_acc, 0, sizeof(unsigned long long) * F.nacc(), st));
@@ -634,13 +559,7 @@ int sf_lammps_ave_histo_cost(void* ptr, const char* id, double* ms)
   for (const std::vector<int>& which : sf::launch_groups(F)) {
     sf::HTable T;
     const long long n = sf::build_table(L, F, which, &T);
-    SF_HIP(hipEventRecord(ev[0], st));
-    sf::launch_table(L, H, F, T, n, H.cost_acc);
-    SF_HIP(hipEventRecord(ev[1], st));
-    SF_HIP(hipStreamSynchronize(st));
-    float t = 0.f;
-    SF_HIP(hipEventElapsedTime(&t, ev[0], ev[1]));
-    total += (double)t;
+    total += sf::stream_ms(st, [&] { sf::launch_table(L, H, F, T, n, H.cost_acc); });
   }
   *ms = total;
   SF_API_END(0)

@@ -1,9 +1,9 @@
 // sf_histo_parse.h -- the words of `fix ID group ave/histo Nevery Nrepeat Nfreq lo hi Nbin value ... keywords`, the bins
 // they define, the bin of one value and the averaging of the output blocks (the rules of DESIGN.md section 16, LAMMPS names
 // and wording), on the host with nothing but the standard library, so that this code can be compiled into a stand-alone
-// program and run under the host sanitizers (sf_global_parse.h is the precedent; it and sf_chunk_parse.h hold the shared
-// pieces: split_quoted, chunk_parse_int / _double, global_parse_cref, ave_first_valid).  The parser returns an empty string,
-// or the error text.  histo_bin is also what the kernel of sf_histo.hip calls: one expression on both sides.
+// program and run under the host sanitizers (sf_global_parse.h is the precedent; sf_chunk_parse.h holds split_quoted and
+// chunk_parse_double; the schedule, the file, ave and start keywords, the attribute words and parse_cref are those of
+// sf_ave_common.h).  The parser returns an empty string, or the error text.  histo_bin is also what the kernel of sf_histo.hip calls: one expression on both sides.
 #pragma once
 #include <deque>
 #include <string>
@@ -21,35 +21,27 @@ namespace sf {
 
 constexpr int kHistoMaxBins = 8192;   // Nbin: the kernel keeps a block's counters in LDS
 constexpr int kHistoMaxValues = 16;   // the columns of one launch (kGCols of sf_global.hip)
-enum HistoAttr { HA_X, HA_Y, HA_Z, HA_VX, HA_VY, HA_VZ, HA_FX, HA_FY, HA_FZ, HA_COMPUTE };
 enum HistoMode { HM_SCALAR, HM_VECTOR };
 enum HistoKind { HK_NONE = -1, HK_GLOBAL, HK_PERATOM, HK_LOCAL };
 enum HistoBeyond { HB_IGNORE, HB_END, HB_EXTRA };
-enum HistoAve { HV_ONE, HV_RUNNING, HV_WINDOW };
 
 struct HistoValue {
-  int attr = HA_X;
+  int attr = AA_X;
   std::string word;   // as typed
-  std::string id;     // HA_COMPUTE
-  long index = 0;     // HA_COMPUTE: k of c_ID[k], 0: none
+  std::string id;     // AA_COMPUTE
+  long index = 0;     // AA_COMPUTE: k of c_ID[k], 0: none
 };
 
-struct HistoSpec {
+struct HistoSpec : AveSchedule, AveFileSpec {
   std::string id, group;
-  long nevery = 1, nrepeat = 1, nfreq = 1;
   double lo = 0.0, hi = 1.0;
   long nbin = 1;
   std::vector<HistoValue> values;
   int mode = HM_SCALAR;
   int kind = HK_NONE;   // as typed (HK_NONE: not given)
   int beyond = HB_IGNORE;
-  int ave = HV_ONE;
+  int ave = AVE_ONE;
   long window = 0;
-  long start = 0;
-  std::string file;
-  bool overwrite = false;
-  bool has_title[3] = {false, false, false};
-  std::string title[3];
 };
 
 // the bins: plain data, the kernel takes it by value
@@ -113,30 +105,25 @@ inline std::string parse_ave_histo(const std::vector<std::string>& w, HistoSpec*
   HistoSpec S;
   S.id = w[1];
   S.group = w[2];
-  if (!chunk_parse_int(w[4], &S.nevery) || !chunk_parse_int(w[5], &S.nrepeat) || !chunk_parse_int(w[6], &S.nfreq)) return illegal;
-  if (S.nevery <= 0 || S.nrepeat <= 0 || S.nfreq <= 0) return illegal;
-  if (S.nfreq % S.nevery || S.nrepeat * S.nevery > S.nfreq) return illegal;
+  if (!S.parse(w, 4, illegal).empty()) return illegal;
   if (!chunk_parse_double(w[7], &S.lo) || !chunk_parse_double(w[8], &S.hi) || !chunk_parse_int(w[9], &S.nbin)) return illegal;
   if (S.lo >= S.hi || S.nbin <= 0) return illegal;
   if (S.nbin > kHistoMaxBins)
     return "fix ave/histo: more than 8192 bins (a block of the binning kernel keeps its counters in LDS)";
-  static const char* const plain[9] = {"x", "y", "z", "vx", "vy", "vz", "fx", "fy", "fz"};
   size_t k = 10;
   for (; k < w.size(); k++) {
     const std::string& s = w[k];
     HistoValue v;
     v.word = s;
-    int a = -1;
-    for (int q = 0; q < 9; q++)
-      if (s == plain[q]) a = q;
+    const int a = ave_attr_of(s);
     if (a >= 0) v.attr = a;
     else if (s.compare(0, 2, "f_") == 0 || s.compare(0, 2, "v_") == 0)
       return "fix ave/histo: " + s + " is not supported (f_ and v_ values are not; x y z vx vy vz fx fy fz, c_ID and c_ID[k] are)";
     else if (s.compare(0, 2, "c_") == 0) {
-      v.attr = HA_COMPUTE;
+      v.attr = AA_COMPUTE;
       if (s.size() > 3 && s.compare(s.size() - 3, 3, "[*]") == 0)
         return "fix ave/histo: " + s + " is not supported (name the columns one by one: c_ID[1] c_ID[2] ...)";
-      if (!global_parse_cref(s, &v.id, &v.index)) return illegal;
+      if (!parse_cref(s, &v.id, &v.index)) return illegal;
     } else
       break;
     if ((int)S.values.size() >= kHistoMaxValues) return "fix ave/histo: more than 16 values";
@@ -146,6 +133,10 @@ inline std::string parse_ave_histo(const std::vector<std::string>& w, HistoSpec*
   while (k < w.size()) {
     const std::string& key = w[k];
     const size_t left = w.size() - k - 1;
+    AveKey shared = ave_file_keyword(w, &k, &S);
+    if (shared == AK_NOT_MINE) shared = ave_mode_keyword(w, &k, &S.ave, &S.window, &S.start);
+    if (shared == AK_ERROR) return illegal;
+    if (shared == AK_CONSUMED) continue;
     if (key == "mode") {
       if (left < 1) return illegal;
       if (w[k + 1] == "scalar") S.mode = HM_SCALAR;
@@ -166,34 +157,8 @@ inline std::string parse_ave_histo(const std::vector<std::string>& w, HistoSpec*
       else if (w[k + 1] == "extra") S.beyond = HB_EXTRA;
       else return illegal;
       k += 2;
-    } else if (key == "ave") {
-      if (left < 1) return illegal;
-      if (w[k + 1] == "one") S.ave = HV_ONE, k += 2;
-      else if (w[k + 1] == "running") S.ave = HV_RUNNING, k += 2;
-      else if (w[k + 1] == "window") {
-        if (left < 2 || !chunk_parse_int(w[k + 2], &S.window) || S.window <= 0 || S.window > 100000) return illegal;
-        S.ave = HV_WINDOW;
-        k += 3;
-      } else
-        return illegal;
-    } else if (key == "start") {
-      if (left < 1 || !chunk_parse_int(w[k + 1], &S.start) || S.start < 0) return illegal;
-      k += 2;
-    } else if (key == "file") {
-      if (left < 1 || w[k + 1].empty()) return illegal;
-      S.file = w[k + 1];
-      k += 2;
     } else if (key == "append") {
       return "fix ave/histo: append is not supported (file is: the file is written anew)";
-    } else if (key == "overwrite") {
-      S.overwrite = true;
-      k += 1;
-    } else if (key == "title1" || key == "title2" || key == "title3") {
-      if (left < 1) return illegal;
-      const int t = key[5] - '1';
-      S.has_title[t] = true;
-      S.title[t] = w[k + 1];
-      k += 2;
     } else
       return illegal;
   }
@@ -211,14 +176,14 @@ struct HistoBlock {
 
 // ave one | running | window M over the blocks as they come (counts are whole numbers below 2^53: the sums are exact)
 struct HistoAverager {
-  int ave = HV_ONE;
+  int ave = AVE_ONE;
   long window = 0;
   HistoBlock run;                  // running: the sum of all blocks
   std::deque<HistoBlock> blocks;   // window: the last M blocks
   HistoBlock add(const HistoBlock& b)
   {
-    if (ave == HV_ONE) return b;
-    if (ave == HV_RUNNING) {
+    if (ave == AVE_ONE) return b;
+    if (ave == AVE_RUNNING) {
       if (run.count.empty()) run.count.assign(b.count.size(), 0.0);
       fold(&run, b);
       return run;

@@ -15,13 +15,13 @@
 #include <vector>
 
 #include "../../include/sedifoam_amd.h"
+#include "sf_ave_fix.h"
 #include "sf_chunk.h"
 #include "sf_compute_atom.h"
 #include "sf_contacts.h"
 #include "sf_dump.h"
 #include "sf_env.h"
 #include "sf_global.h"
-#include "sf_handles.h"
 #include "sf_histo.h"
 #include "sf_restart.h"
 #include "sf_rigid.h"
@@ -157,13 +157,13 @@ void advance(SfLammps& L, int n)
 // destination, a restart schedule or such a fix the run is not cut.
 void sf::run_steps(SfLammps& L, int n)
 {
-  const bool thermo = sf::thermo_active(L), rst = sf::restart_active(L), avc = sf::ave_chunk_active(L);
-  const bool avt = sf::ave_time_active(L), avh = sf::ave_histo_active(L);
+  const bool thermo = sf::thermo_active(L), rst = sf::restart_active(L);
+  const bool ave = sf::ave_fix_next_step(L, L.eng.nsteps()) >= 0;   // (there is an averaging fix)
   if (thermo && L.eng.rigid_on() && sf::thermo_needs_dof(L))
     sf::fail("thermo output with temp / press / ke / etotal / p** needs the degrees of freedom of the rigid bodies, which "
              "fix rigid/nve does not keep yet: use thermo_style custom without them, or -screen none -log none");
   sf::restart_run_begin(L);   // (wall rows of a restart file that no fix claimed are dropped here; host only)
-  if (!sf::dump_active(L) && !thermo && !rst && !avc && !avt && !avh) {
+  if (!sf::dump_active(L) && !thermo && !rst && !ave) {
     L.eng.set_thermo_virial(false);
     advance(L, n);
     return;
@@ -171,16 +171,9 @@ void sf::run_steps(SfLammps& L, int n)
   if (thermo) sf::thermo_run_begin(L);   // (the first run: the virial of the setup evaluation)
   advance(L, 0);   // (setup: the frame of the first step holds the forces of the setup evaluation)
   sf::dump_write_due(L);
-  if (avc) sf::ave_chunk_sample_due(L);   // (a sample whose step is this one: fix ave/chunk samples at the setup of a run)
-  // the global computes of this step, one plan: the fix ave/time samples due, the c_ columns of the thermo line and the
-  // global inputs of the fix ave/histo samples due; then those samples bin the values where they lie on the device
-  auto globals_and_histos_due = [&](bool setup) {
-    std::vector<std::string> ids = sf::thermo_global_ids_due(L, setup, setup ? n : 0);
-    if (avh) sf::ave_histo_global_ids_due(L, &ids);
-    if (avt || thermo || !ids.empty()) sf::global_step_due(L, ids);
-    if (avh) sf::ave_histo_sample_due(L);
-  };
-  globals_and_histos_due(true);
+  // the samples of the averaging fixes whose step is this one (they sample at the setup of a run too), and in the same plan
+  // of global computes the c_ columns of the thermo line
+  sf::ave_fix_step_due(L, sf::thermo_global_ids_due(L, true, n));
   if (thermo) sf::thermo_setup(L, n);
   const long long end = L.eng.nsteps() + (n > 0 ? n : 0);
   while (L.eng.nsteps() < end) {
@@ -191,22 +184,10 @@ void sf::run_steps(SfLammps& L, int n)
       sf::thermo_arm(L, next);   // (the pair virial of step `next`, when it has a line that shows pressure)
     }
     if (rst) next = std::min(next, sf::restart_next_step(L, L.eng.nsteps()));
-    if (avc) {
-      const long long nx = sf::ave_chunk_next_step(L, L.eng.nsteps());
-      if (nx >= 0) next = std::min(next, nx);
-    }
-    if (avt) {
-      const long long nx = sf::ave_time_next_step(L, L.eng.nsteps());
-      if (nx >= 0) next = std::min(next, nx);
-    }
-    if (avh) {
-      const long long nx = sf::ave_histo_next_step(L, L.eng.nsteps());
-      if (nx >= 0) next = std::min(next, nx);
-    }
+    if (ave) next = std::min(next, sf::ave_fix_next_step(L, L.eng.nsteps()));
     advance(L, (int)(next - L.eng.nsteps()));
     sf::dump_write_due(L);
-    if (avc) sf::ave_chunk_sample_due(L);
-    globals_and_histos_due(false);
+    sf::ave_fix_step_due(L, sf::thermo_global_ids_due(L, false, 0));
     if (rst) sf::restart_write_due(L);
     if (thermo) sf::thermo_write_due(L);
   }

@@ -123,6 +123,10 @@ int main()
   ave_bad("5 1 10 c c_s[0]", "Illegal fix ave/chunk");
   ave_bad("5 1 10 c c_s[1]x", "Illegal fix ave/chunk");
   ave_bad("5 1 10 c c_[2]", "Illegal fix ave/chunk");
+  ave_bad("5 1 10 c c_s[+1]", "Illegal fix ave/chunk");   // (an index is digits and nothing else, as in LAMMPS)
+  ave_bad("5 1 10 c \"c_s[ 1]\"", "Illegal fix ave/chunk");
+  ave_bad("5 1 10 c c_s]", "Illegal fix ave/chunk");
+  ave_bad("5 1 10 c c_s[1000001]", "Illegal fix ave/chunk");
   ave_bad("5 1 10 c vx ave window 5", "ave window");
   ave_bad("5 1 10 c vx norm", "Illegal fix ave/chunk");
   ave_bad("5 1 10 c vx norm both", "Illegal fix ave/chunk");

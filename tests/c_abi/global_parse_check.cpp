@@ -96,8 +96,8 @@ int main()
   {
     sf::ReduceSpec S;
     const std::string e = reduce("sum c_st[6] vy", &S);
-    expect(e.empty() && S.inputs[0].attr == sf::GA_COMPUTE && S.inputs[0].id == "st" && S.inputs[0].index == 6 &&
-               S.inputs[0].word == "c_st[6]" && S.inputs[1].attr == sf::GA_VY && S.id == "r" && S.group == "all",
+    expect(e.empty() && S.inputs[0].attr == sf::AA_COMPUTE && S.inputs[0].id == "st" && S.inputs[0].index == 6 &&
+               S.inputs[0].word == "c_st[6]" && S.inputs[1].attr == sf::AA_VY && S.id == "r" && S.group == "all",
            "reduce sum c_st[6] vy (fields)", e);
   }
   reduce_bad("", illegal);
@@ -163,14 +163,14 @@ int main()
   {
     sf::AveTimeSpec S;
     const std::string e = avet("5 2 10 c_a c_b[3] ave window 7 start 25 file f.txt title1 \"# a b\" format \" %.3f\"", &S);
-    expect(e.empty() && S.nevery == 5 && S.nrepeat == 2 && S.nfreq == 10 && S.ave == sf::AT_WINDOW && S.window == 7 &&
+    expect(e.empty() && S.nevery == 5 && S.nrepeat == 2 && S.nfreq == 10 && S.ave == sf::AVE_WINDOW && S.window == 7 &&
                S.start == 25 && S.file == "f.txt" && S.has_title[0] && S.title[0] == "# a b" && !S.has_title[1] &&
                S.format == " %.3f" && S.values[1].id == "b" && S.values[1].index == 3 && S.values[1].word == "c_b[3]" &&
                !S.overwrite,
            "ave/time (fields)", e);
     sf::AveTimeSpec D;
     const std::string d = avet("1 1 1 c_a", &D);
-    expect(d.empty() && D.format == " %g" && D.ave == sf::AT_ONE && D.start == 0 && D.file.empty(), "ave/time (defaults)", d);
+    expect(d.empty() && D.format == " %g" && D.ave == sf::AVE_ONE && D.start == 0 && D.file.empty(), "ave/time (defaults)", d);
   }
   avet_bad("", bad);
   avet_bad("2 3", bad);

@@ -62,16 +62,16 @@ int main()
   {
     sf::HistoSpec S = histo_ok("2 3 10 -1.5 2.5 40 vx vy vz mode vector", 3);
     expect(S.nevery == 2 && S.nrepeat == 3 && S.nfreq == 10 && S.lo == -1.5 && S.hi == 2.5 && S.nbin == 40 && S.mode == sf::HM_VECTOR &&
-               S.beyond == sf::HB_IGNORE && S.ave == sf::HV_ONE && S.kind == sf::HK_NONE && S.values[2].attr == sf::HA_VZ,
+               S.beyond == sf::HB_IGNORE && S.ave == sf::AVE_ONE && S.kind == sf::HK_NONE && S.values[2].attr == sf::AA_VZ,
            "  its fields", "");
     S = histo_ok("1 1 1 0 1 8192 c_r", 1);
-    expect(S.mode == sf::HM_SCALAR && S.values[0].attr == sf::HA_COMPUTE && S.values[0].id == "r" && S.values[0].index == 0, "  its fields", "");
+    expect(S.mode == sf::HM_SCALAR && S.values[0].attr == sf::AA_COMPUTE && S.values[0].id == "r" && S.values[0].index == 0, "  its fields", "");
     S = histo_ok("1 1 1 0 1 10 c_s[4] c_k x mode vector kind peratom beyond extra ave window 3 start 20 file out.txt overwrite", 3);
     expect(S.values[0].id == "s" && S.values[0].index == 4 && S.values[0].word == "c_s[4]" && S.kind == sf::HK_PERATOM &&
-               S.beyond == sf::HB_EXTRA && S.ave == sf::HV_WINDOW && S.window == 3 && S.start == 20 && S.file == "out.txt" && S.overwrite,
+               S.beyond == sf::HB_EXTRA && S.ave == sf::AVE_WINDOW && S.window == 3 && S.start == 20 && S.file == "out.txt" && S.overwrite,
            "  its fields", "");
     S = histo_ok("5 2 10 0 1 10 c_pl[2] mode vector kind local beyond end ave running", 1);
-    expect(S.kind == sf::HK_LOCAL && S.beyond == sf::HB_END && S.ave == sf::HV_RUNNING, "  its fields", "");
+    expect(S.kind == sf::HK_LOCAL && S.beyond == sf::HB_END && S.ave == sf::AVE_RUNNING, "  its fields", "");
     S = histo_ok("1 1 1 0 1 10 c_r kind global mode scalar ave one beyond ignore", 1);
     expect(S.kind == sf::HK_GLOBAL && S.mode == sf::HM_SCALAR, "  its fields", "");
     // quoted titles
@@ -85,7 +85,7 @@ int main()
     S = histo_ok("1 1 1 0 1 10 vx mode scalar mode vector kind global kind peratom beyond end beyond extra ave running ave window 2 "
                  "ave one start 5 start 7 file a file b overwrite overwrite title1 a title1 b title2 a title2 b title3 a title3 b",
                  1);
-    expect(S.mode == sf::HM_VECTOR && S.kind == sf::HK_PERATOM && S.beyond == sf::HB_EXTRA && S.ave == sf::HV_ONE && S.start == 7 &&
+    expect(S.mode == sf::HM_VECTOR && S.kind == sf::HK_PERATOM && S.beyond == sf::HB_EXTRA && S.ave == sf::AVE_ONE && S.start == 7 &&
                S.file == "b" && S.overwrite && S.title[0] == "b" && S.title[1] == "b" && S.title[2] == "b",
            "  the last of each keyword", "");
     histo_ok("1 1 1 0 1 10 x y z vx vy vz fx fy fz c_a c_b c_c c_d c_e c_f c_g mode vector", 16);
@@ -186,8 +186,8 @@ int main()
     const sf::HistoBlock b[4] = {block({1, 1, 0, 0}, 2, 0, 0.5, 1.5), block({0, 0, 1, 0}, 1, 1, 2.5, 9.0),
                                  block({0, 0, 0, 2}, 2, 1, -1.0, 3.5), block({1, 0, 0, 0}, 1, 0, 0.5, 0.5)};
     sf::HistoAverager one, run, win;
-    run.ave = sf::HV_RUNNING;
-    win.ave = sf::HV_WINDOW;
+    run.ave = sf::AVE_RUNNING;
+    win.ave = sf::AVE_WINDOW;
     win.window = 2;
     sf::HistoBlock o, r, w;
     for (int k = 0; k < 4; k++) o = one.add(b[k]), r = run.add(b[k]), w = win.add(b[k]);

@@ -395,6 +395,11 @@ def _decompose(lmp):
      "Dump local compute does not compute local info: k is a per-atom compute"),
     (_plain, ["compute k all ke/atom", "dump d all custom 10 {p} id c_k"], "uncompute k",
      "a dump custom still uses this compute"),
+    # (an index is digits and nothing else, at most 1000000, and nothing follows the `]`: parse_cref of sf_ave_common.h)
+    (_plain, ["compute s all stress/atom"], "dump d all custom 10 {p} id c_s[+1]", "Invalid attribute c_s[+1] in dump custom"),
+    (_plain, ["compute s all stress/atom"], "dump d all custom 10 {p} id c_s]", "Invalid attribute c_s] in dump custom"),
+    (_plain, ["compute s all stress/atom"], "dump d all custom 10 {p} id c_s[1000001]",
+     "Invalid attribute c_s[1000001] in dump custom"),
 ])
 def test_refused_forms(make, before, line, msg, tmp_path):
     lmp = make()
