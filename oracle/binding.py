@@ -103,6 +103,10 @@ def _declare(L):
     L.orc_dem_get_history.argtypes = [C.c_void_p, C.c_int, ip, ip, dp]
     L.orc_dem_get_history.restype = C.c_int
     L.orc_dem_get_wall_shear.argtypes = [C.c_void_p, C.c_int, dp]
+    L.orc_dem_get_mass.argtypes = [C.c_void_p, dp]
+    L.orc_dem_add_atoms.argtypes = [C.c_void_p, C.c_int, dp, ip, C.c_double, C.c_double, dp, C.c_int]
+    L.orc_dem_delete_atoms.argtypes = [C.c_void_p, C.c_int, ip]
+    L.orc_dem_delete_atoms.restype = C.c_int
     vp = C.c_void_p
     L.orc_dem_set_subdomain.argtypes = [vp, C.c_double, C.c_double]
     L.orc_dem_local_particle_volume.restype = C.c_double
@@ -334,6 +338,31 @@ class OracleDem:
         self.L.orc_dem_get_wall_shear(self.h, w, P(sh))
         self.L.orc_dem_get(self.h, None, None, None, None, None, P(tag))
         return sh[np.argsort(tag, kind="stable")]
+
+    def mass(self):
+        """rmass of the local atoms sorted by tag"""
+        n = self.nlocal
+        m = np.zeros(n)
+        tag = np.zeros(n, dtype=np.int32)
+        self.L.orc_dem_get_mass(self.h, P(m))
+        self.L.orc_dem_get(self.h, None, None, None, None, None, P(tag))
+        return m[np.argsort(tag, kind="stable")]
+
+    def create_particle(self, position, tag, diameter, rho, type_, vel, active_bit=0):
+        """lammps_create_particle (library.cpp:406-490) under the product's contract: the atoms are appended, the
+        survivors' history is kept by partner tag, the lists are rebuilt at the call (once a setup has run).  type_ is
+        accepted for the signature's sake (the oracle has no per-type data); active_bit: the bit of group `active`
+        where the script defines it (library.cpp:448-451), 0 otherwise."""
+        position = f64(position).reshape(-1, 3)
+        tag = i32(np.asarray(tag).astype(np.int64))
+        assert len(tag) == position.shape[0]
+        self.L.orc_dem_add_atoms(self.h, position.shape[0], P(position), P(tag), float(diameter), float(rho),
+                                 P(f64(vel)), int(active_bit))
+
+    def delete_particle(self, tags):
+        """lammps_delete_particle (library.cpp:492-621) under the product's contract; returns the number removed"""
+        tags = i32(tags)
+        return self.L.orc_dem_delete_atoms(self.h, tags.shape[0], P(tags))
 
 
 class OracleSlabEngine:

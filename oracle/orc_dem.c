@@ -702,3 +702,141 @@ void orc_dem_get_wall_shear(const orc_dem *d, int w, double *shear)
       idx++;
     }
 }
+
+void orc_dem_get_mass(const orc_dem *d, double *rmass)
+{
+  memcpy(rmass, d->rmass, sizeof(double) * (size_t)d->nlocal);
+}
+
+/* ---- lammps_create_particle / lammps_delete_particle (library.cpp:406-621) --------------------------------------
+ *
+ * The contract restated here is the one the product documents, NOT the reference's control flow.  In the reference
+ * the forced reneighbour is commented out (library.cpp:611; only next_reneighbor is set, :482-486 and :607-612) and
+ * `avec->copy(last, i)` (library.cpp:587-592) moves the last atom into the hole while the old list still points at
+ * the old indices: until the next list build the pairs of the moved atoms read a stranger's history.  The product
+ * instead keeps the survivors' history BY PARTNER TAG and rebuilds the lists at the call, before the next force.
+ *
+ * At the call, on the positions the call sees:
+ *   1. the history of the old list is copied out per atom and partner tag (orc__partners_from_list: what
+ *      FixShearHistory::pre_exchange does before any rebuild [3P]);
+ *   2. the listed atoms leave every per-atom array by an order-preserving compaction -- records, tag, mask, f, torque,
+ *      the fdrag rows (ffluiddrag, DuDt, vOld), every wall's shear, the partner rows -- or the new atoms are appended:
+ *      mass by library.cpp:460 with its literal, omega, f, torque and every fix row zero;
+ *   3. the ghosts are dropped (library.cpp:476-480, :600-604);
+ *   4. pbc, ghosts and lists are made again (orc__build_lists stores xhold and counts the build).
+ * No force is evaluated: lammps_step is `run n pre no` (library.cpp:379), so the first half-kick of the next step uses
+ * the stored forces -- which still hold the contributions of the atoms that left.  Before the first setup there is
+ * no list and nothing is built: the atoms only join or leave the arrays.
+ */
+static void copy_owned(orc_dem *d, int to, int from)
+{
+  int k, w;
+  for (k = 0; k < 3; k++) {
+    d->x[3 * to + k] = d->x[3 * from + k];
+    d->v[3 * to + k] = d->v[3 * from + k];
+    d->omega[3 * to + k] = d->omega[3 * from + k];
+    d->f[3 * to + k] = d->f[3 * from + k];
+    d->torque[3 * to + k] = d->torque[3 * from + k];
+    d->ffluiddrag[3 * to + k] = d->ffluiddrag[3 * from + k];
+    d->DuDt[3 * to + k] = d->DuDt[3 * from + k];
+    d->vOld[3 * to + k] = d->vOld[3 * from + k];
+    d->xhold[3 * to + k] = d->xhold[3 * from + k];
+  }
+  d->radius[to] = d->radius[from];
+  d->rmass[to] = d->rmass[from];
+  d->tag[to] = d->tag[from];
+  d->mask[to] = d->mask[from];
+  for (w = 0; w < d->nfix; w++)
+    if (d->fix[w].kind == FIX_WALL)
+      for (k = 0; k < 3; k++) d->fix[w].wshear[3 * to + k] = d->fix[w].wshear[3 * from + k];
+}
+
+static void rebuild_after_edit(orc_dem *d, orc_partners *ps)
+{
+  d->nghost = 0;
+  if (!d->setup_done) { /* no list yet: orc_dem_setup builds the first one */
+    free(ps->pfirst); free(ps->ptag); free(ps->pshear);
+    return;
+  }
+  orc__pbc(d);
+  orc__make_ghosts(d);
+  orc__build_lists(d, ps);
+}
+
+void orc_dem_add_atoms(orc_dem *d, int n, const double *x, const int *tag, double diameter, double rho,
+                       const double *vel, int mask)
+{
+  int n0 = d->nlocal, m, k, w;
+  orc_partners ps;
+  if (n <= 0) return;
+  orc__partners_from_list(d, &ps);   /* before the new atoms take the ghosts' places: the list still names ghosts */
+  orc__grow_atoms(d, n0 + n);
+  orc__ensure_local_cap(d, n0 + n);
+  ps.pfirst = orc__xrealloc(ps.pfirst, sizeof(int) * ((size_t)n0 + n + 1));
+  for (m = 0; m < n; m++) {
+    int i = n0 + m;
+    double radtmp = 0.5 * diameter;
+    for (k = 0; k < 3; k++) {
+      d->x[3 * i + k] = x[3 * m + k];
+      d->v[3 * i + k] = vel[k];
+      d->omega[3 * i + k] = d->f[3 * i + k] = d->torque[3 * i + k] = 0.0;
+      d->ffluiddrag[3 * i + k] = d->DuDt[3 * i + k] = d->vOld[3 * i + k] = 0.0;
+    }
+    d->radius[i] = radtmp;
+    d->rmass[i] = 4.0 * 3.14159265358917323846 / 3.0 * radtmp * radtmp * radtmp * rho;   /* library.cpp:460, literal kept */
+    d->tag[i] = tag[m];
+    d->mask[i] = 1 | mask;
+    for (w = 0; w < d->nfix; w++)
+      if (d->fix[w].kind == FIX_WALL)
+        for (k = 0; k < 3; k++) d->fix[w].wshear[3 * i + k] = 0.0;
+    ps.pfirst[i + 1] = ps.pfirst[i];   /* new atoms start without contacts */
+  }
+  d->nlocal = n0 + n;
+  rebuild_after_edit(d, &ps);
+}
+
+static int cmp_int(const void *a, const void *b)
+{
+  int p = *(const int *)a, q = *(const int *)b;
+  return (p > q) - (p < q);
+}
+
+int orc_dem_delete_atoms(orc_dem *d, int n, const int *tags)
+{
+  int n0 = d->nlocal, i, k, m, ndel = 0;
+  int *del, *mark;
+  orc_partners ps;
+  if (n <= 0 || !n0) return 0;
+  del = malloc(sizeof(int) * (size_t)n);
+  mark = calloc((size_t)n0, sizeof(int));
+  memcpy(del, tags, sizeof(int) * (size_t)n);
+  qsort(del, (size_t)n, sizeof(int), cmp_int);
+  for (i = 0; i < n0; i++)
+    if (bsearch(&d->tag[i], del, (size_t)n, sizeof(int), cmp_int)) {
+      mark[i] = 1;
+      ndel++;
+    }
+  free(del);
+  if (!ndel) { /* nothing of this list is owned: nothing changes, nothing is rebuilt */
+    free(mark);
+    return 0;
+  }
+  orc__partners_from_list(d, &ps);
+  k = 0;
+  for (i = 0; i < n0; i++) {
+    if (mark[i]) continue;
+    int b = ps.pfirst[i], e = ps.pfirst[i + 1], q;   /* (read before pfirst[k + 1] is written: k <= i) */
+    int nb = ps.pfirst[k];
+    for (m = b; m < e; m++) {
+      ps.ptag[nb + (m - b)] = ps.ptag[m];
+      for (q = 0; q < 3; q++) ps.pshear[3 * (nb + (m - b)) + q] = ps.pshear[3 * m + q];
+    }
+    ps.pfirst[k + 1] = nb + (e - b);
+    if (k != i) copy_owned(d, k, i);
+    k++;
+  }
+  free(mark);
+  d->nlocal = k;
+  rebuild_after_edit(d, &ps);
+  return ndel;
+}

@@ -90,6 +90,7 @@ typedef struct {
 
 void *orc__xrealloc(void *p, size_t n);
 void orc__grow_atoms(orc_dem *d, int nmax);
+void orc__ensure_local_cap(orc_dem *d, int n);   /* orc_halo.c: the per-owned-atom arrays hold n atoms */
 void orc__pbc(orc_dem *d);
 void orc__make_ghosts(orc_dem *d);
 void orc__forward_comm(orc_dem *d);

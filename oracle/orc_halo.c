@@ -34,7 +34,7 @@ static orc_fix *wall_of(orc_dem *d, int idx)
   return NULL;
 }
 
-static void ensure_local_cap(orc_dem *d, int n)
+void orc__ensure_local_cap(orc_dem *d, int n)
 {
   int w, i;
   if (n <= d->localcap) return;
@@ -271,7 +271,7 @@ void orc_dem_migrate_unpack(orc_dem *d, const double *buf, long ndoubles)
   compact(d);
   if (!n) return;
   int n0 = d->nlocal;
-  ensure_local_cap(d, n0 + n);
+  orc__ensure_local_cap(d, n0 + n);
   /* room in the partner table */
   d->pcnt = orc__xrealloc(d->pcnt, sizeof(int) * (size_t)(n0 + n));
   d->ptab = orc__xrealloc(d->ptab, sizeof(int) * (size_t)(n0 + n) * (W ? W : 1));
@@ -398,7 +398,7 @@ void orc_dem_rebuild_finish(orc_dem *d)
   /* partner table -> CSR for the list build */
   orc_partners ps;
   int n = d->nlocal, i, m, W = d->mrec;
-  ensure_local_cap(d, n);
+  orc__ensure_local_cap(d, n);
   ps.pfirst = calloc((size_t)n + 1, sizeof(int));
   for (i = 0; i < n; i++) ps.pfirst[i + 1] = ps.pfirst[i] + (d->have_ptab ? d->pcnt[i] : 0);
   ps.ptag = malloc(sizeof(int) * (size_t)(ps.pfirst[n] ? ps.pfirst[n] : 1));

@@ -201,6 +201,16 @@ void orc_dem_put_fdrag(orc_dem *d, int n, const double *fdrag, const int *tag);
 int orc_dem_get_history(const orc_dem *d, int max, int *tag_i, int *tag_j, double *shear);
 /* per-atom wall shear of wall w (AoS 3*nlocal, driver order) */
 void orc_dem_get_wall_shear(const orc_dem *d, int w, double *shear);
+/* rmass of the local atoms, driver order */
+void orc_dem_get_mass(const orc_dem *d, double *rmass);
+
+/* lammps_create_particle / lammps_delete_particle (library.cpp:406-621) under the contract the product documents: the
+ * survivors' history is kept by partner tag and the lists are rebuilt at the call, no force evaluation (see orc_dem.c).
+ * add: n atoms of one diameter, density and velocity (x: 3*n, tag: n), mask = the group bits of a new atom (1 = all).
+ * delete: returns how many owned atoms were removed (unknown tags are ignored, a tag named twice counts once). */
+void orc_dem_add_atoms(orc_dem *d, int n, const double *x, const int *tag, double diameter, double rho,
+                       const double *vel, int mask);
+int orc_dem_delete_atoms(orc_dem *d, int n, const int *tags);
 
 /* ---- one slab of an x-decomposed domain (orc_halo.c): same calls and record layouts as the product's
  * sf_dem_* halo entry points, so sedifoam_amd/halo.py can be driven on CPUs (gloo) ---- */

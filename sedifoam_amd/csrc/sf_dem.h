@@ -658,7 +658,7 @@ private:
   };
   void permute_locals(const int* perm, int n_new, bool rows = true, const RankJob* rank = nullptr);
   void migrate_compact();
-  void compute_partner_tags();
+  void compute_partner_tags(bool allow_in_place = true);
   int select_locals(int mode, double bound, DevArray& list, int dim = 0);
  public:
   long long migrate_count();   // owned atoms outside [sublo, subhi): what the two migrate_pack calls would send
@@ -773,6 +773,8 @@ private:
   bool trigger_rearmed_ = false;     // F_TRIGGER was set back to INT_MAX by k_back_slots of this rebuild
   int park_rows_ = 0;                // LDS parking rows of the next list build (0: as many as list slots)
   bool hist_in_place_ = false;   // this rebuild's list build reads the old list in place (compute_partner_tags)
+  bool hist_in_place_env_ = true;   // SF_HIST_IN_PLACE
+  bool build_lds_env_ = true;       // SF_BUILD_LDS
   bool build_parks_in_lds() const;
   // During a rebuild shear_[hist_buf_] holds the OLD list's history expanded to a copy per side (what partner tags
   // address: migration, re-injection); the new list's history is built into the other buffer, which then becomes

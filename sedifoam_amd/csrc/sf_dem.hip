@@ -129,6 +129,8 @@ DemEngine::DemEngine()
   roots_ = !opt_lds_;
   if ((opt_sub_env_ = env_override("SF_SUB", opt_sub_))) opt_sub_ = std::max(1, opt_sub_);
   hist_mode_env_ = env_int("SF_HIST_COPIES", hist_mode_env_);
+  hist_in_place_env_ = env_flag("SF_HIST_IN_PLACE", hist_in_place_env_);
+  build_lds_env_ = env_flag("SF_BUILD_LDS", build_lds_env_);
   touch_prefetch_env_ = env_int("SF_TOUCH_PREFETCH", touch_prefetch_env_);
   touch_first_env_ = env_int("SF_TOUCH_FIRST", touch_first_env_);
   nt_policy_env_ = env_int("SF_NT_POLICY", nt_policy_env_);
@@ -1303,11 +1305,10 @@ static constexpr size_t kBuildLdsMax = 160 * 1024;
 
 bool DemEngine::build_parks_in_lds() const
 {
-  static const bool env = env_flag("SF_BUILD_LDS", true);
-  return env && (size_t)M_ * kBuildLdsPerSlot <= kBuildLdsMax / 2;
+  return build_lds_env_ && (size_t)M_ * kBuildLdsPerSlot <= kBuildLdsMax / 2;
 }
 
-void DemEngine::compute_partner_tags()
+void DemEngine::compute_partner_tags(bool allow_in_place)
 {
   // the old list's history by partner tag, a copy per SIDE of every contact, in the ping-pong buffer the sub-steps
   // are not using: what migration packs and what the list build re-injects
@@ -1316,9 +1317,10 @@ void DemEngine::compute_partner_tags()
   // the order they index, the current history buffer) and writes the new words into the other word array -- no staging
   // pass (98 of a 1 M-grain loose bed's 774 us per rebuild, 15 of a 100 k bed's 210).  The staged rows remain what
   // migration packs (decomposed domains) and what the tiled / LDS-staged builds read.
-  static const bool in_place_env = env_flag("SF_HIST_IN_PLACE", true);
-  hist_in_place_ = in_place_env && build_parks_in_lds() && !have_subdomain_ && roots_ && grid_.tile <= 1 && !opt_lds_ &&
-                   have_list_ && nlocal_ > 0 && max_neigh_used_ > 0;
+  // allow_in_place = false: a compaction follows (permute_locals with rows) before the list is built -- the old words index
+  // the order of BEFORE it, so the rows have to be staged and travel with their atoms (delete_particles)
+  hist_in_place_ = allow_in_place && hist_in_place_env_ && build_parks_in_lds() && !have_subdomain_ && roots_ &&
+                   grid_.tile <= 1 && !opt_lds_ && have_list_ && nlocal_ > 0 && max_neigh_used_ > 0;
   if (hist_in_place_) {
     hist_buf_ = cur_;   // (k_build_neigh reads shear_[hist_buf_] and writes shear_[hist_buf_ ^ 1])
     return;
@@ -1354,6 +1356,8 @@ void DemEngine::permute_locals(const int* perm, int n_new, bool rows, const Rank
 {
   order_version_++;
   hist_indirect_ = false;
+  // (a list read in place has no staged rows to gather: its words index the order this call is about to change twice)
+  if (rows && hist_in_place_) fail("permute_locals: rows of a list that is read in place (compute_partner_tags(false) stages them)");
   if (n_new <= 0) return;
   const int nb = div_up(n_new, 256);
   // gather into the scratch array of the same shape, then swap the two allocations (no copy back): everything

@@ -1191,6 +1191,12 @@ void DemEngine::create_particles(int np, const double* pos, const double* tag, d
     max_tag_ = std::max(max_tag_, ht[k]);
   }
   rmax_ = std::max(rmax_, r);
+  // Words that index ghost SLOTS (the LDS-staged form; the other forms name a root and an image code): the new atoms take
+  // the slots of the first ghosts, and with them the tags the old list's history is found by -- the copy of an
+  // owned-ghost pair on the owned side lost its history, unseen by get_history where the other side has the lower tag.
+  // Stage the history by partner tag while the ghosts are still there.
+  const bool stage_first = setup_done_ && !have_subdomain_ && have_list_ && !roots_ && nghost_ > 0;
+  if (stage_first) compute_partner_tags(/*allow_in_place=*/false);
   // ghosts are dropped (library.cpp:476-480 resets nghost) and re-created by the forced rebuild below
   const size_t o4 = sizeof(double4) * nlocal_, oi = sizeof(int) * nlocal_;
   auto up = [&](DevArray& a, const void* src, size_t bytes, size_t off) {
@@ -1227,7 +1233,16 @@ void DemEngine::create_particles(int np, const double* pos, const double* tag, d
   order_version_++;
   nghost_ = 0;
   // next_reneighbor = ntimestep + 1 for every fix (library.cpp:482-486): rebuild before the next force
-  if (setup_done_ && !have_subdomain_) rebuild();
+  if (setup_done_ && !have_subdomain_) {
+    if (stage_first) {   // (the rows are staged already: rebuild() without its rebuild_begin, as delete_particles)
+      if (!in_run_) predict_.external(nsteps_);
+      compute_grid();
+      next_ghost_ = 0;
+      rebuild_sort();
+      rebuild_finish();
+    } else
+      rebuild();
+  }
 }
 
 void DemEngine::delete_particles(const int* tags, int n)
@@ -1246,8 +1261,8 @@ void DemEngine::delete_particles(const int* tags, int n)
     }
   if (!ndel) return;
   if (have_list_) {
-    // the history of the surviving atoms must outlive the compaction
-    compute_partner_tags();
+    // the history of the surviving atoms must outlive the compaction: staged by partner tag, never read in place
+    compute_partner_tags(/*allow_in_place=*/false);
   }
   SF_HIP(hipMemcpyAsync(leave_.ptr, leave.data(), sizeof(int) * nlocal_, hipMemcpyHostToDevice, stream_));
   migrate_leavers_ = ndel;

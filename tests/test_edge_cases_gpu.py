@@ -6,6 +6,7 @@ import pytest
 from sedifoam_amd import synthetic
 from tests import dem_cases as dc
 import tests.test_dem_gpu as T
+import tests.test_inject_remove_gpu as IR
 
 pytestmark = pytest.mark.gpu
 
@@ -175,21 +176,26 @@ def test_create_and_delete_particles():
     lmp.setup()
     lmp.step(10)
     n0 = lmp.get_local_n()
-    h0 = lmp.history()
     top = float(bed["x"][:, 1].max())
     pos = np.array([[1.0e-3, top + 2.0e-3, 1.0e-3], [3.0e-3, top + 2.0e-3, 2.0e-3]])
+    before = IR._snap(lmp, cfg)
     lmp.create_particle(pos, [n0 + 1, n0 + 2], 0.8e-3, 2000.0, 1, [0.0, -0.1, 0.0])
     assert lmp.get_local_n() == n0 + 2 and lmp.get_global_n() == n0 + 2
+    # old atoms, their contacts and their history survive the call bit for bit; the new atoms bring no contact
+    live, dropped = IR._assert_carried(before, IR._snap(lmp, cfg), [], "create")
+    assert len(before["hist"]) > 0 and dropped == 0
     ii = lmp.get_initial_info()
     k = int(np.nonzero(ii["tag"] == n0 + 1)[0][0])
     assert ii["diam"][k] == pytest.approx(0.8e-3) and ii["rho"][k] == pytest.approx(2000.0, rel=1e-12)
     assert np.allclose(ii["v"][k], [0.0, -0.1, 0.0])
     lmp.step(5)
-    h1 = lmp.history()
-    assert set(h0) <= set(h1) or len(set(h0) - set(h1)) < 5        # old contacts (and their history) survive
     dead = [1, 5, n0 + 2]
+    before = IR._snap(lmp, cfg)
     lmp.delete_particle(dead)
     assert lmp.get_local_n() == n0 - 1
+    # the history is the one before minus every pair that holds a dead tag, value for value
+    live, dropped = IR._assert_carried(before, IR._snap(lmp, cfg), dead, "delete")
+    assert dropped > 0
     tags = set(lmp.get_local_info()["tag"].tolist())
     assert not (tags & set(dead)) and (n0 + 1) in tags
     lmp.step(20)
