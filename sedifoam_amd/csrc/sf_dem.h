@@ -327,6 +327,9 @@ struct RebuildPredictor {
   }
 };
 
+struct GhostPtrs;   // sf_dem_rebuild.h
+struct ListStats;   // sf_list_policy.h
+
 class DemEngine {
  public:
   DemEngine();
@@ -663,8 +666,23 @@ private:
  public:
   long long migrate_count();   // owned atoms outside [sublo, subhi): what the two migrate_pack calls would send
  private:
-  void make_periodic_ghosts();
-  void bin_and_build();
+  GhostPtrs ghost_ptrs() const;
+  void make_periodic_ghosts(bool wait_for_count = false);
+  // the list build and its steps, in their order (sf_dem.hip, bin_and_build)
+  struct ListBuild;
+  enum class BuildOutcome { done, widen_rows, more_parking_rows, ghosts_over_capacity };
+  bool bin_and_build();
+  void prepare_list_build();
+  void choose_list_layout();
+  void sort_ghosts_into_cells();
+  void count_sort_uncounted_ghosts();
+  void count_sort_ghosts();
+  void radix_sort_ghosts();
+  void clear_build_counters();
+  ListBuild list_build_params(int attempt);
+  void launch_list_build(const ListBuild& lb);
+  BuildOutcome read_build_outcome(const ListBuild& lb);
+  void adopt_new_list();
   void read_flags();
   void reset_flag(int idx, int value);
   void reset_flags(int idx, int count, int value);   // `count` adjacent flags, one launch
@@ -681,9 +699,9 @@ private:
   size_t cap_ = 0;
   int nlocal_ = 0, nghost_ = 0, next_ghost_ = 0;   // next_ghost_: external ghosts appended by border_unpack
                                                    // nghost_ < 0 (inside a rebuild only): the count is still on the device --
-                                                   // make_periodic_ghosts did not wait for it, bin_and_build reads it with its flags
-  bool ghost_sync_ = false;                        // bin_and_build: a deferred count overflowed the capacity -- make the ghosts
-                                                   // again and wait for the count
+                                                   // set by make_periodic_ghosts, which did not wait for it; sort_ghosts_into_cells
+                                                   // and the list build run on the device's count, read_build_outcome reads it
+                                                   // with the flags of the first attempt
   int cur_ = 0;
   int M_ = 32;
   int max_neigh_used_ = 0;
@@ -769,16 +787,30 @@ private:
   DevArray neigh_, numneigh_, shear_[2];
   DevArray neigh_old_, numneigh_old_, ptag_;   // B-side buffers swapped in by permute/build
   int flags_seq_ = 0;                // sequence number of the last flag publication (flags_copy_begin / _wait)
-  bool build_flags_clean_ = false;   // the list build's counters were zeroed by k_pbc_keys of this rebuild
-  bool trigger_rearmed_ = false;     // F_TRIGGER was set back to INT_MAX by k_back_slots of this rebuild
-  int park_rows_ = 0;                // LDS parking rows of the next list build (0: as many as list slots)
-  bool hist_in_place_ = false;   // this rebuild's list build reads the old list in place (compute_partner_tags)
+  // State of one rebuild: who sets it, who consumes it
+  // the list build's counters are zero: set by rebuild_sort (k_pbc_keys zeroes them), spent by clear_build_counters of the
+  // first attempt -- later attempts launch a reset
+  bool build_flags_clean_ = false;
+  // LDS parking rows of the next list build (0: as many as list slots): set by adopt_new_list from the longest row,
+  // consumed -- and widened to M_ from the second attempt on -- by list_build_params, compared by read_build_outcome
+  int park_rows_ = 0;
+  // this rebuild's list build reads the old list in place: set by compute_partner_tags (rebuild_begin, or the callers that
+  // compact first and pass false), checked by permute_locals (no rows of such a list may be gathered), consumed by
+  // list_build_params (source and destination word arrays), cleared by adopt_new_list
+  bool hist_in_place_ = false;
+  // the rebuild's knobs, read by the constructor
   bool hist_in_place_env_ = true;   // SF_HIST_IN_PLACE
   bool build_lds_env_ = true;       // SF_BUILD_LDS
+  bool rank_permute_env_ = true;    // SF_RANK_PERMUTE
+  bool ghost_defer_env_ = true;     // SF_GHOST_DEFER
+  int park_margin_env_ = 8;         // SF_PARK_MARGIN
+  bool build_quad_set_ = false;     // SF_BUILD_QUAD was given ...
+  int build_quad_env_ = 0;          // ... as this many lanes per atom (not given: by grid_.stencil, per build)
   bool build_parks_in_lds() const;
   // During a rebuild shear_[hist_buf_] holds the OLD list's history expanded to a copy per side (what partner tags
   // address: migration, re-injection); the new list's history is built into the other buffer, which then becomes
-  // shear_[cur_]
+  // shear_[cur_].  Set by compute_partner_tags (cur_ when the list is read in place), flipped by permute_locals when it
+  // gathers the rows, consumed by launch_list_build and adopt_new_list
   int hist_buf_ = 0;
   // one history copy per contact (true) or one per side (false): chosen per list build from the measured coalescing
   // of the previous list (SF_HIST_COPIES=1 / 2 pins it)
@@ -804,9 +836,9 @@ private:
   RebuildPredictor predict_;                 // single-domain run(): how far to queue (SF_QUEUE_PREDICT=0: everything)
   int nt_policy_ = 2, nt_policy_env_ = -1;   // non-temporal policy of the row streams (sf_dem_kernels.h, NTP)
   void measure_list();     // queue k_partner_coalescing on the current list (results with the next flag read)
-  bool list_stats_near_a_threshold() const;
+  ListStats list_stats() const;   // the four counters of the last measurement, as the flag words hold them on the host
   long long list_sampled_ = 0;   // atoms the last measure_list looked at
-  void choose_kernel();    // pick touch_prefetch_ from the last measurement
+  void choose_kernel();    // nt_policy_, sort_sub_ and touch_prefetch_ from the last measurement (sf_list_policy.h)
   DevArray nloc_;                      // [M][cap] uint16 (see DemPtrs::nloc)
   int* tile_tab_ = nullptr;            // [2][ntiles] tile_first / tile_last, then [ntiles+1] counts, starts
   size_t tile_alloc_ = 0;
@@ -821,11 +853,38 @@ private:
   // (one scratch array per permuted array: permute_locals gathers everything in one launch and swaps allocations)
   DevArray tmp4b_, tmp4c_, tmpi_b_, tmpi_c_, tmpi_d_, fdrag_alt_, DuDt_alt_, vOld_alt_, extra_alt_, wtouch_alt_;
   DevArray keys_, keys_alt_, perm_, perm_alt_, keys64_, keys64_alt_;
-  int* cell_start_ = nullptr;          // [nbins][4]: owned start/end, ghost start/end of every cell (hipMalloc: 16-byte aligned)
+  // The cell tables: 4 * cell_alloc_ ints (hipMalloc: 16-byte aligned, and cell_alloc_ a multiple of four keeps every row
+  // table so), in one of two layouts -- row_tables_ says which.  Addressed through the two views below only.
+  int* cell_start_ = nullptr;
   size_t cell_alloc_ = 0;
+  // row_tables_ (plain keys, counting sort): four tables of cell_alloc_ ints.  The histograms are counted back down to
+  // zero by the kernels that place the atoms (hist_clean_); the scans are the reversed lower-bound tables the list build reads
+  struct CellRowTables {
+    int* own_count;     // histogram of the owned atoms
+    int* own_first;     // first sorted position of every cell
+    int* ghost_count;   // histogram of the ghosts
+    int* ghost_first;   // first position of every cell in the ghost order
+  };
+  CellRowTables cell_row_tables() const
+  {
+    return {cell_start_, cell_start_ + cell_alloc_, cell_start_ + 2 * cell_alloc_, cell_start_ + 3 * cell_alloc_};
+  }
+  // !row_tables_ (tiled / LDS-staged keys, radix sort): [nbins][4], the four columns interleaved per cell
+  struct CellRanges {
+    static constexpr int stride = 4;
+    int* own_start;
+    int* own_end;
+    int* ghost_start;
+    int* ghost_end;
+  };
+  CellRanges cell_ranges() const { return {cell_start_, cell_start_ + 1, cell_start_ + 2, cell_start_ + 3}; }
   DevArray hist_perm_;        // see permute_locals(rows = false)
+  // the old rows are read through hist_perm_: set by permute_locals(rows = false) of rebuild_sort, consumed by
+  // list_build_params (BuildParams::old_index), cleared by adopt_new_list and by every other permute_locals
   bool hist_indirect_ = false;
-  bool row_tables_ = false;   // cell_start_ holds the reversed lower-bound tables (plain keys) instead of cell ranges
+  // which layout cell_start_ holds: set by rebuild_sort, consumed by make_periodic_ghosts (may the count stay on the
+  // device?), sort_ghosts_into_cells, list_build_params and launch_list_build
+  bool row_tables_ = false;
   int* tagmap_ = nullptr;
   size_t tagmap_alloc_ = 0;
   long long order_version_ = 0, tagmap_builds_ = -1;   // the tag -> index table is rebuilt when the atom order changed
@@ -888,7 +947,10 @@ private:
   long long nsend_[2] = {0, 0};
   int recv_first_[2] = {0, 0}, recv_count_[2] = {0, 0};
   hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
-  bool hist_clean_ = false;   // the cell histograms of cell_start_ are all zero (their users count them back down)
+  // the two histograms of the row tables are all zero (the kernels that place the atoms count them back down): set by
+  // rebuild_sort and the two counting sorts of the ghosts behind their last kernel, false while one is in flight, after the
+  // range layout was written and after compute_grid made a new table; consumed by rebuild_sort (memset or not)
+  bool hist_clean_ = false;
   long long prof_rebuilds_ = 0;
   double prof_rebuild_ms_ = 0.0;
   hipEvent_t ev_flags_ = nullptr;   // "the flag words have reached the host" (bin_and_build)

@@ -17,6 +17,7 @@
 #include "sf_dem_io.h"
 #include "sf_env.h"
 #include "sf_dem_lds_kernel.h"
+#include "sf_list_policy.h"
 #include "sf_rigid.h"
 #include "sf_roctx.h"
 #include "sf_thermo.h"
@@ -131,6 +132,10 @@ DemEngine::DemEngine()
   hist_mode_env_ = env_int("SF_HIST_COPIES", hist_mode_env_);
   hist_in_place_env_ = env_flag("SF_HIST_IN_PLACE", hist_in_place_env_);
   build_lds_env_ = env_flag("SF_BUILD_LDS", build_lds_env_);
+  rank_permute_env_ = env_flag("SF_RANK_PERMUTE", rank_permute_env_);
+  build_quad_set_ = env_override("SF_BUILD_QUAD", build_quad_env_);
+  ghost_defer_env_ = env_flag("SF_GHOST_DEFER", ghost_defer_env_);
+  park_margin_env_ = env_int("SF_PARK_MARGIN", park_margin_env_);
   touch_prefetch_env_ = env_int("SF_TOUCH_PREFETCH", touch_prefetch_env_);
   touch_first_env_ = env_int("SF_TOUCH_FIRST", touch_first_env_);
   nt_policy_env_ = env_int("SF_NT_POLICY", nt_policy_env_);
@@ -1450,14 +1455,14 @@ void DemEngine::rebuild_sort()
     pb.wrap[k] = periodic_[k] && !ext_[k];
   }
   const int nb = div_up(nlocal_, 256);
-  // Plain keys (no tiles, no LDS staging): counting sort.  cell_start_ = [0] histogram of the owned atoms | [1] first
-  // sorted position of every cell (owned) | [2] histogram of the ghosts | [3] first position in the ghost order.  The
+  // Plain keys (no tiles, no LDS staging): counting sort into the row tables of cell_start_ (CellRowTables).  The
   // histograms are counted back down to zero by the kernels that use them: cleared only when the table is new.
   row_tables_ = grid_.tile <= 1 && !opt_lds_;
-  int* count = row_tables_ ? cell_start_ : nullptr;
+  const CellRowTables rt = cell_row_tables();
+  int* count = row_tables_ ? rt.own_count : nullptr;
   if (row_tables_ && !hist_clean_) {
-    SF_HIP(hipMemsetAsync(cell_start_, 0, sizeof(int) * cell_alloc_, stream_));
-    SF_HIP(hipMemsetAsync(cell_start_ + 2 * cell_alloc_, 0, sizeof(int) * cell_alloc_, stream_));
+    SF_HIP(hipMemsetAsync(rt.own_count, 0, sizeof(int) * cell_alloc_, stream_));
+    SF_HIP(hipMemsetAsync(rt.ghost_count, 0, sizeof(int) * cell_alloc_, stream_));
   }
   hist_clean_ = false;   // (until the kernels below have run: an error in between leaves it dirty)
   k_pbc_keys<<<nb, 256, 0, stream_>>>(xr_[cur_].as<double4>(), nlocal_, pb, grid_, keys_.as<unsigned>(),
@@ -1465,14 +1470,13 @@ void DemEngine::rebuild_sort()
   build_flags_clean_ = true;   // (F_NEIGH_OVER, F_MAXNEIGH zeroed by that kernel: the first list build needs no reset launch)
   if (row_tables_) {
     const int ne = grid_.nbins + 1;
-    int* first = cell_start_ + cell_alloc_;
+    int* first = rt.own_first;
     exclusive_scan_i32(sort_tmp_, sort_tmp_bytes_, count, first, ne, stream_);
     k_key_place<<<nb, 256, 0, stream_>>>(keys_.as<unsigned>(), nlocal_, count, first, perm_.as<int>());
     hist_clean_ = true;
     // (rank and permutation in one launch: a launch less in a chain that small beds find bound by its launches -- 100 k loose
     // bed +0.9 to +2.4 % whole run; the scattered stores cost the 1 M bed nothing, +0.1 to +1 %: profiles/r06_rank_permute_ab.txt)
-    const bool fused_rank = env_flag("SF_RANK_PERMUTE", true);
-    if (fused_rank) {
+    if (rank_permute_env_) {
       const RankJob rj{keys_.as<unsigned>(), first, perm_.as<int>()};
       permute_locals(perm_alt_.as<int>(), nlocal_, /*rows=*/false, &rj);
     } else {
@@ -1491,8 +1495,9 @@ void DemEngine::rebuild_sort()
     // sorted bin keys -> cell ranges of owned atoms
     hist_clean_ = false;
     SF_HIP(hipMemsetAsync(cell_start_, 0, sizeof(int) * 4 * cell_alloc_, stream_));
-    k_cell_bounds<unsigned><<<nb, 256, 0, stream_>>>(keys_alt_.as<unsigned>(), nlocal_, 0, cell_start_,
-                                                     cell_start_ + 1, 4);
+    const CellRanges cr = cell_ranges();
+    k_cell_bounds<unsigned><<<nb, 256, 0, stream_>>>(keys_alt_.as<unsigned>(), nlocal_, 0, cr.own_start, cr.own_end,
+                                                     CellRanges::stride);
   }
   // owned range of every tile (bin keys are tile-major: key >> log2(T^3) is the tile id)
   const int T = grid_.tile;
@@ -1511,7 +1516,15 @@ void DemEngine::rebuild_sort()
   }
 }
 
-void DemEngine::make_periodic_ghosts()
+GhostPtrs DemEngine::ghost_ptrs() const
+{
+  return GhostPtrs{xr_[cur_].as<double4>(), vm_[cur_].as<double4>(), om_[cur_].as<double4>(), tag_.as<int>(),
+                   type_.as<int>(), mask_.as<int>(), gsrc_.as<int>(), gshift_.as<double>()};
+}
+
+// wait_for_count: read the ghost count here even where it could stay on the device (bin_and_build, after a deferred count
+// overflowed the capacity)
+void DemEngine::make_periodic_ghosts(bool wait_for_count)
 {
   // external ghosts (other GPUs) were appended by border_unpack: slots [nlocal, nlocal+next_ghost_)
   nghost_ = next_ghost_;
@@ -1522,8 +1535,7 @@ void DemEngine::make_periodic_ghosts()
   for (int dim = 0; dim < 3; dim++)   // images across an external face come from the neighbour GPUs (or the driver's self loop)
     if (periodic_[dim] && !ext_[dim]) dims[nd++] = dim;
   if (!nd || cap_ == 0 || nlocal_ + next_ghost_ == 0) return;
-  GhostPtrs G{xr_[cur_].as<double4>(), vm_[cur_].as<double4>(), om_[cur_].as<double4>(), tag_.as<int>(),
-              type_.as<int>(), mask_.as<int>(), gsrc_.as<int>(), gshift_.as<double>()};
+  GhostPtrs G = ghost_ptrs();
   for (int attempt = 0; attempt < 4; attempt++) {
     // F_GHOST_COUNT counts ghosts (external ones included); list slot = ghost slot.  Every dimension looks at the owned
     // atoms + the ghosts made before it; those counts stay on the device (k_ghost_select), the host reads the total
@@ -1539,8 +1551,7 @@ void DemEngine::make_periodic_ghosts()
     }
     // (the count can stay on the device until the flags are read behind the list build: bin_and_build; nghost_ < 0 =
     // "on the device".  SF_GHOST_DEFER=0: read it here, as before round 5)
-    static const bool defer = env_flag("SF_GHOST_DEFER", true);
-    if (defer && attempt == 0 && row_tables_ && !ghost_sync_) {
+    if (ghost_defer_env_ && attempt == 0 && row_tables_ && !wait_for_count) {
       nghost_ = -1;
       return;
     }
@@ -1551,8 +1562,7 @@ void DemEngine::make_periodic_ghosts()
     }
     // (a count cut short by the capacity is a lower bound of what is needed)
     ensure_capacity((size_t)nlocal_ + (size_t)h_flags_[F_GHOST_COUNT] * 2 + 1024);
-    G = GhostPtrs{xr_[cur_].as<double4>(), vm_[cur_].as<double4>(), om_[cur_].as<double4>(), tag_.as<int>(),
-                  type_.as<int>(), mask_.as<int>(), gsrc_.as<int>(), gshift_.as<double>()};
+    G = ghost_ptrs();
   }
   fail("ghost creation: capacity could not be grown");
 }
@@ -1574,13 +1584,10 @@ void DemEngine::build_stage_tables()
   }
   int* tcount = tile_tab_ + 2 * tile_alloc_;
   int* tstart = tile_tab_ + 3 * tile_alloc_;
-  int* cellLS = cell_start_;        // interleaved per cell: {owned start, owned end, ghost start, ghost end}
-  int* cellLE = cell_start_ + 1;
-  int* cellGS = cell_start_ + 2;
-  int* cellGE = cell_start_ + 3;
+  const CellRanges cr = cell_ranges();
   reset_flag(F_STAGE_MAX, 0);
-  k_tile_stage_count<<<div_up(ntiles_, 128), 128, 0, stream_>>>(grid_, cellLS, cellLE, cellGS, cellGE, ntiles_,
-                                                               tcount, d_flags_);
+  k_tile_stage_count<<<div_up(ntiles_, 128), 128, 0, stream_>>>(grid_, cr.own_start, cr.own_end, cr.ghost_start,
+                                                               cr.ghost_end, ntiles_, tcount, d_flags_);
   exclusive_scan_i32(sort_tmp_, sort_tmp_bytes_, tcount, tstart, ntiles_ + 1, stream_);
   int total = 0;
   SF_HIP(hipMemcpyAsync(&total, tstart + ntiles_, sizeof(int), hipMemcpyDeviceToHost, stream_));
@@ -1592,202 +1599,274 @@ void DemEngine::build_stage_tables()
     stage_alloc_ = (size_t)total + total / 8 + 1024;
     SF_HIP(hipMalloc(&stage_idx_, sizeof(int) * stage_alloc_));
   }
-  k_tile_stage_fill<<<div_up(ntiles_, 128), 128, 0, stream_>>>(grid_, cellLS, cellLE, cellGS, cellGE,
-                                                              perm_alt_.as<int>(), ntiles_, tstart, eoff_,
+  k_tile_stage_fill<<<div_up(ntiles_, 128), 128, 0, stream_>>>(grid_, cr.own_start, cr.own_end, cr.ghost_start,
+                                                              cr.ghost_end, perm_alt_.as<int>(), ntiles_, tstart, eoff_,
                                                               stage_idx_);
   lds_active_ = true;
 }
 
-void DemEngine::bin_and_build()
+// what list_build_params works out for one attempt of the list build
+struct DemEngine::ListBuild {
+  BuildParams B;
+  bool parked_in_lds;   // the row path with its parked candidates in LDS (lds_bytes of them per block)
+  size_t lds_bytes;
+  int* new_words;       // where the new list goes: the other word array when the old one is read in place
+};
+
+// The list build (rebuild_finish, behind the sort and the ghosts) as a driver over its steps, in their order:
+//   choose_list_layout, sort_ghosts_into_cells, build_stage_tables -- once per list;
+//   clear_build_counters, list_build_params, launch_list_build, read_build_outcome -- per attempt;
+//   adopt_new_list -- once.
+// Returns whether the trigger word was re-armed on the device (by k_back_slots, the last kernel of every attempt).
+bool DemEngine::bin_and_build()
 {
   if (!nlocal_) {
     have_list_ = true;
-    return;
+    return false;
   }
-  // history copies of this list: from the coalescing the previous list measured (h_flags_ was refreshed by the
-  // synchronisation that led here), with hysteresis; the first list is built single-copy
-  if (hist_mode_env_ == 1) hist_single_ = true;
-  else if (hist_mode_env_ == 2 || !roots_) hist_single_ = false;
-  else if (have_list_ && h_flags_[F_PART_SLOTS] > 0) {
-    const double frac = (double)h_flags_[F_PART_COAL] / (double)h_flags_[F_PART_SLOTS];
-    if (hist_single_ && frac < 0.45) hist_single_ = false;
-    else if (!hist_single_ && frac > 0.60) hist_single_ = true;
-    if (debug_hist()) fprintf(stderr, "[sedifoam_amd] partner-side coalescing %.3f -> %s history copy\n", frac, hist_single_ ? "one" : "two");
-  }
-  // slot order of this list: touching neighbours first when the previous list touched fewer than about half of what
-  // it listed (k_build_neigh, touch_first; hysteresis 0.40 / 0.50; SF_TOUCH_FIRST=0 / 1 pins it)
-  if (touch_first_env_ >= 0) touch_first_ = touch_first_env_ != 0;
-  else if (have_list_ && h_flags_[F_LIST_SLOTS] > 0) {
-    const double frac = (double)h_flags_[F_LIST_TOUCH] / (double)h_flags_[F_LIST_SLOTS];
-    const bool before = touch_first_;
-    if (!touch_first_ && frac < 0.40) touch_first_ = true;
-    else if (touch_first_ && frac > 0.50) touch_first_ = false;
-    if (debug_hist() && before != touch_first_)
-      fprintf(stderr, "[sedifoam_amd] %.3f of the listed neighbours touch -> touching neighbours %s\n", frac,
-              touch_first_ ? "first in their rows" : "in candidate order");
-  }
-  int* cellLS = cell_start_;        // interleaved per cell: {owned start, owned end, ghost start, ghost end}
-  int* cellLE = cell_start_ + 1;
-  int* cellGS = cell_start_ + 2;
-  int* cellGE = cell_start_ + 3;
-  // (nghost_ < 0: the ghost count is still on the device -- make_periodic_ghosts did not wait for it; the kernels below read
-  // it themselves and are launched for the most ghosts the capacity could hold)
-  const bool ghosts_pending = nghost_ < 0;
-  if (ghosts_pending && !row_tables_) fail("bin_and_build: deferred ghost count without row tables");
-  if (ghosts_pending) {
-    const int ne = grid_.nbins + 1;
-    const int ng = std::max(1, div_up((long long)(cap_ - (size_t)nlocal_), 256));
-    int* count = cell_start_ + 2 * cell_alloc_;
-    int* first = cell_start_ + 3 * cell_alloc_;
-    hist_clean_ = false;
-    k_ghost_cells_dev<<<ng, 256, 0, stream_>>>(xr_[cur_].as<double4>(), nlocal_, cap_, grid_, keys_.as<unsigned>(), count,
-                                               d_flags_);
-    exclusive_scan_i32(sort_tmp_, sort_tmp_bytes_, count, first, ne, stream_);
-    k_key_place_dev<<<ng, 256, 0, stream_>>>(keys_.as<unsigned>(), d_flags_, nlocal_, cap_, count, first, perm_.as<int>());
-    k_key_rank_dev<<<ng, 256, 0, stream_>>>(keys_.as<unsigned>(), d_flags_, nlocal_, cap_, first, perm_.as<int>(),
-                                            tag_.as<int>(), perm_alt_.as<int>());
-    hist_clean_ = true;
-  } else if (nghost_ && row_tables_) {
-    // ghosts in (cell, tag) order by the same counting sort as the owned atoms; its scan IS the table of first
-    // ghost-order positions per cell that the list build reads
-    const int ne = grid_.nbins + 1, ng = div_up(nghost_, 256);
-    int* count = cell_start_ + 2 * cell_alloc_;
-    int* first = cell_start_ + 3 * cell_alloc_;
-    hist_clean_ = false;
-    k_ghost_cells<<<ng, 256, 0, stream_>>>(xr_[cur_].as<double4>(), nlocal_, nghost_, grid_, keys_.as<unsigned>(), count,
-                                           d_flags_);
-    exclusive_scan_i32(sort_tmp_, sort_tmp_bytes_, count, first, ne, stream_);
-    k_key_place<<<ng, 256, 0, stream_>>>(keys_.as<unsigned>(), nghost_, count, first, perm_.as<int>());
-    k_key_rank<<<ng, 256, 0, stream_>>>(keys_.as<unsigned>(), nghost_, first, perm_.as<int>(), tag_.as<int>(),
-                                        perm_alt_.as<int>(), nlocal_);
-    hist_clean_ = true;
-  } else if (nghost_) {
-    k_ghost_keys<<<div_up(nghost_, 256), 256, 0, stream_>>>(xr_[cur_].as<double4>(), tag_.as<int>(), nlocal_,
-                                                            nghost_, grid_, keys64_.as<unsigned long long>(),
-                                                            perm_.as<int>(), d_flags_);
-    sort_pairs_u64(sort_tmp_, sort_tmp_bytes_, keys64_.as<unsigned long long>(),
-                   keys64_alt_.as<unsigned long long>(), perm_.as<int>(), perm_alt_.as<int>(), nghost_, 64,
-                   stream_);
-    k_cell_bounds<unsigned long long><<<div_up(nghost_, 256), 256, 0, stream_>>>(
-        keys64_alt_.as<unsigned long long>(), nghost_, 32, cellGS, cellGE, 4);
-  }
-  build_stage_tables();
-  for (int attempt = 0; attempt < 4; attempt++) {
-    if (build_flags_clean_) h_flags_[F_NEIGH_OVER] = h_flags_[F_MAXNEIGH] = 0;
-    else set_flags3(F_NEIGH_OVER, 0, F_MAXNEIGH, 0, F_PARK_OVER, 0);
-    build_flags_clean_ = false;
-    BuildParams B;
-    B.nlocal = nlocal_;
-    B.M = M_;
-    B.Mold = max_neigh_used_;
-    B.cap = cap_;
-    B.skin_gran = gran_.style ? lskin() : -1.0;
-    B.cut_lub = lub_.enabled ? lub_.cut_global + lskin() : 0.0;
-    // fix cohesive walks a regular half list (fix_cohesive.cpp:75-77), whose criterion is the pair cutoff + skin for
-    // every pair, not ri + rj + skin: pairs enter that list exactly when LAMMPS would list them
-    if (cohe_.enabled) B.cut_lub = std::max(B.cut_lub, cutneighmax());
-    B.g = grid_;
-    B.eoff = lds_active_ ? eoff_ : nullptr;
-    B.nloc = nloc_.as<unsigned short>();
-    B.old_index = hist_indirect_ ? hist_perm_.as<int>() : nullptr;
-    B.two_copies = hist_single_ ? 0 : 1;
-    B.touch_first = touch_first_ ? 1 : 0;
-    B.lb_own = row_tables_ ? cell_start_ + cell_alloc_ : nullptr;
-    B.lb_ghost = (row_tables_ && nghost_) ? cell_start_ + 3 * cell_alloc_ : nullptr;   // (nghost_ < 0: on the device)
-    // parked candidates in LDS (row path): as long as the rows fit; a list read in place needs them there (the scratch
-    // rows of the other form ARE the word array the new list goes into)
-    const bool lc = row_tables_ && (hist_in_place_ || build_parks_in_lds());
-    // (parking rows: the longest row of the previous list + 8 -- a fifth of the LDS of a compute unit per block otherwise,
-    // at four waves per SIMD; an atom with more candidates than that reports F_PARK_OVER and the list is built again)
-    if (park_rows_ <= 0 || park_rows_ > M_ || attempt > 0) park_rows_ = M_;
-    B.P = park_rows_;
-    const size_t lds_bytes = lc ? (size_t)park_rows_ * kBuildLdsPerSlot : 0;
-    if (lds_bytes > kBuildLdsMax)
-      fail("neighbor list rows of more than %d slots do not fit the list build's LDS rows (SF_HIST_IN_PLACE=0 SF_BUILD_LDS=0 "
-           "builds such lists through memory)", (int)(kBuildLdsMax / kBuildLdsPerSlot));
-    static bool lds_attr_set = false;
-    if (lc && !lds_attr_set) {
-      SF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_build_neigh<true>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBuildLdsMax));
-      SF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_build_neigh_quad<4>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBuildLdsMax));
-      SF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_build_neigh_quad<2>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBuildLdsMax));
-      SF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_build_neigh_quad<8>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBuildLdsMax));
-      lds_attr_set = true;
-    }
-    B.old_words = hist_in_place_ ? neigh_.as<int>() : nullptr;
-    B.old_tag = hist_in_place_ ? tmpi_.as<int>() : nullptr;   // (permute_locals swapped the old tag array out into tmpi_)
-    int* const new_words = hist_in_place_ ? neigh_old_.as<int>() : neigh_.as<int>();
-    B.roots = roots_ ? 1 : 0;
-    B.gsrc = gsrc_.as<int>();
-    B.gshift = gshift_.as<double>();
-    for (int k = 0; k < 3; k++) {
-      B.inv_prd[k] = 1.0 / (boxhi_[k] - boxlo_[k]);
-      B.prd[k] = boxhi_[k] - boxlo_[k];
-    }
-    if (roots_ && cap_ > (size_t)kIdxMask) fail("more than %d atom slots per GPU: not addressable by the neighbour word", kIdxMask);
-    // four lanes per atom on four consecutive records (k_build_neigh_quad): single domain without a ghost pass
-    // (rows of full-cutoff cells -- loose beds, ~8 records -- keep four lanes busy: 405 -> 297 us on the loose 1 M bed, 60 -> 39 us
-    // at 100 k grains)
-    // (the 25 rows of 2-3 records of a packed bed's half-cutoff cells: two lanes, 399 -> 347-355 us at 1 M; four lanes 446)
-    const int lq = env_int("SF_BUILD_QUAD", grid_.stencil == 1 ? 4 : 2);   // (read per build: the tests switch it inside a process)
-    const bool quad = lc && !B.lb_ghost && !grid_.xslow && (lq == 2 || lq == 4 || lq == 8);
-    auto build_quad = [&](auto lanes) {   // (128 / LQ atoms per workgroup of 128 lanes)
-      constexpr int LQ = decltype(lanes)::value;
-      k_build_neigh_quad<LQ><<<div_up(nlocal_, 128 / LQ), 128, lds_bytes / LQ, stream_>>>(
-          B, xr_[cur_].as<double4>(), tag_.as<int>(), old_rows() ? numneigh_.as<int>() : nullptr, ptag_.as<int>(),
-          shear_[hist_buf_].as<double>(), new_words, numneigh_old_.as<int>(), shear_[hist_buf_ ^ 1].as<double>(), d_flags_,
-          xhold_.as<double>());
-    };
-    auto build = [&](auto kernel, int* old_words) {   // (lds_bytes: 0 without parking rows in LDS)
-      kernel<<<div_up(nlocal_, 128), 128, lds_bytes, stream_>>>(
-          B, xr_[cur_].as<double4>(), tag_.as<int>(), cellLS, cellLE, cellGS, cellGE, perm_alt_.as<int>(),
-          old_rows() ? numneigh_.as<int>() : nullptr, ptag_.as<int>(), shear_[hist_buf_].as<double>(), new_words,
-          numneigh_old_.as<int>(), shear_[hist_buf_ ^ 1].as<double>(), d_flags_, old_words, xhold_.as<double>());
-    };
-    if (quad && lq == 2) build_quad(int_c<2>{});
-    else if (quad && lq == 8) build_quad(int_c<8>{});
-    else if (quad) build_quad(int_c<4>{});
-    else if (lc) build(k_build_neigh<true>, nullptr);
-    else if (!row_tables_) build(k_build_neigh<false, false>, neigh_old_.as<int>());
-    else build(k_build_neigh<false>, neigh_old_.as<int>());
-    // the host looks at the counts (overflow, widest row) while the partner-slot pass below is already running: it
-    // needs nothing but the list, and a list that overflowed -- rare -- is built again and the pass repeated
-    flags_copy_begin();
-    // partner slots: where does the owner keep this pair?  (a partner whose owner does not list it back owns the pair)
-    k_back_slots<<<div_up(nlocal_, 128), 128, 0, stream_>>>(new_words, numneigh_old_.as<int>(), nlocal_, cap_,
-                                                            roots_ ? 1 : 0, d_flags_);
-    trigger_rearmed_ = true;
-    flags_copy_wait();
-    if (ghosts_pending && nghost_ < 0) {
-      // the ghost count arrives with these flags.  More ghosts than the capacity held: nothing above saw a ghost -- grow,
-      // make the ghosts again (this time waiting for the count) and start over
-      if (h_flags_[F_GHOST_OVER] || (size_t)nlocal_ + (size_t)h_flags_[F_GHOST_COUNT] > cap_) {
-        ensure_capacity((size_t)nlocal_ + (size_t)h_flags_[F_GHOST_COUNT] * 2 + 1024);
-        ghost_sync_ = true;
-        make_periodic_ghosts();
-        ghost_sync_ = false;
-        bin_and_build();
-        return;
-      }
-      nghost_ = h_flags_[F_GHOST_COUNT];
-    }
-    if (h_flags_[F_NEIGH_OVER] > M_) {
-      // more neighbours than slots: widen the slot-major arrays and build again.  The old-history
-      // arrays keep their first rows, so the re-injection still finds every partner.
-      grow_neigh(h_flags_[F_NEIGH_OVER] + 4);
+  prepare_list_build();
+  for (int attempt = 0; attempt < 4;) {
+    clear_build_counters();
+    const ListBuild lb = list_build_params(attempt);
+    launch_list_build(lb);
+    const BuildOutcome outcome = read_build_outcome(lb);
+    if (outcome == BuildOutcome::done) break;
+    if (outcome == BuildOutcome::ghosts_over_capacity) {
+      // more ghosts than the capacity held: nothing above saw a ghost -- grow, make the ghosts again (this time waiting for
+      // the count) and start over with the first attempt of a new build (the count is on the host now: this happens once)
+      ensure_capacity((size_t)nlocal_ + (size_t)h_flags_[F_GHOST_COUNT] * 2 + 1024);
+      make_periodic_ghosts(/*wait_for_count=*/true);
+      prepare_list_build();
       continue;
     }
-    if (lc && h_flags_[F_PARK_OVER] > park_rows_) continue;   // (again, with as many parking rows as list slots)
-    break;
+    // more neighbours than slots: widen the slot-major arrays and build again.  The old-history arrays keep their first
+    // rows, so the re-injection still finds every partner.  (more_parking_rows: again, with as many rows as list slots)
+    if (outcome == BuildOutcome::widen_rows) grow_neigh(h_flags_[F_NEIGH_OVER] + 4);
+    attempt++;
   }
   if (h_flags_[F_NEIGH_OVER] > M_) fail("neighbor list overflow (%d > %d slots)", h_flags_[F_NEIGH_OVER], M_);
   if (h_flags_[F_LOST] == 1) {
     reset_flag(F_LOST, 0);
     fail("Lost atoms: an atom left the (non-periodic) simulation box");  // thermo_modify lost error
   }
+  adopt_new_list();
+  return true;
+}
+
+// what precedes the attempts of one list build (again after a ghost overflow: the flag words were refreshed since)
+void DemEngine::prepare_list_build()
+{
+  choose_list_layout();
+  sort_ghosts_into_cells();
+  build_stage_tables();
+}
+
+ListStats DemEngine::list_stats() const
+{
+  return ListStats::from_counters(h_flags_[F_PART_SLOTS], h_flags_[F_PART_COAL], h_flags_[F_LIST_SLOTS],
+                                  h_flags_[F_LIST_TOUCH]);
+}
+
+// History copies and slot order of the list about to be built, from what the previous list measured (h_flags_ was
+// refreshed by the synchronisation that led here), each behind its band of sf_list_policy.h; the first list is built
+// single-copy, in candidate order
+void DemEngine::choose_list_layout()
+{
+  const ListStats s = list_stats();
+  hist_single_ = choose_hist_single(hist_single_, s, have_list_, hist_mode_env_, roots_);
+  if (debug_hist() && !hist_copies_pinned(hist_mode_env_, roots_) && have_list_ && s.has_coalescing)
+    fprintf(stderr, "[sedifoam_amd] partner-side coalescing %.3f -> %s history copy\n", s.coalescing, hist_single_ ? "one" : "two");
+  // touching neighbours first when the previous list touched fewer than about half of what it listed (k_build_neigh)
+  const bool before = touch_first_;
+  touch_first_ = choose_touch_first(touch_first_, s, have_list_, touch_first_env_);
+  if (debug_hist() && touch_first_env_ < 0 && before != touch_first_)
+    fprintf(stderr, "[sedifoam_amd] %.3f of the listed neighbours touch -> touching neighbours %s\n", s.touching,
+            touch_first_ ? "first in their rows" : "in candidate order");
+}
+
+// Ghosts in (cell, tag) order, one of three ways.  Row tables: the same counting sort as the owned atoms, whose scan IS the
+// table of first ghost-order positions per cell that the list build reads.
+void DemEngine::sort_ghosts_into_cells()
+{
+  if (nghost_ < 0 && !row_tables_) fail("bin_and_build: deferred ghost count without row tables");
+  if (nghost_ < 0) count_sort_uncounted_ghosts();
+  else if (nghost_ && row_tables_) count_sort_ghosts();
+  else if (nghost_) radix_sort_ghosts();
+}
+
+// nghost_ < 0: the ghost count is still on the device -- make_periodic_ghosts did not wait for it; the kernels read it
+// themselves and are launched for the most ghosts the capacity could hold
+void DemEngine::count_sort_uncounted_ghosts()
+{
+  const int ne = grid_.nbins + 1;
+  const int ng = std::max(1, div_up((long long)(cap_ - (size_t)nlocal_), 256));
+  const CellRowTables rt = cell_row_tables();
+  hist_clean_ = false;
+  k_ghost_cells_dev<<<ng, 256, 0, stream_>>>(xr_[cur_].as<double4>(), nlocal_, cap_, grid_, keys_.as<unsigned>(),
+                                             rt.ghost_count, d_flags_);
+  exclusive_scan_i32(sort_tmp_, sort_tmp_bytes_, rt.ghost_count, rt.ghost_first, ne, stream_);
+  k_key_place_dev<<<ng, 256, 0, stream_>>>(keys_.as<unsigned>(), d_flags_, nlocal_, cap_, rt.ghost_count, rt.ghost_first,
+                                           perm_.as<int>());
+  k_key_rank_dev<<<ng, 256, 0, stream_>>>(keys_.as<unsigned>(), d_flags_, nlocal_, cap_, rt.ghost_first, perm_.as<int>(),
+                                          tag_.as<int>(), perm_alt_.as<int>());
+  hist_clean_ = true;
+}
+
+void DemEngine::count_sort_ghosts()
+{
+  const int ne = grid_.nbins + 1, ng = div_up(nghost_, 256);
+  const CellRowTables rt = cell_row_tables();
+  hist_clean_ = false;
+  k_ghost_cells<<<ng, 256, 0, stream_>>>(xr_[cur_].as<double4>(), nlocal_, nghost_, grid_, keys_.as<unsigned>(),
+                                         rt.ghost_count, d_flags_);
+  exclusive_scan_i32(sort_tmp_, sort_tmp_bytes_, rt.ghost_count, rt.ghost_first, ne, stream_);
+  k_key_place<<<ng, 256, 0, stream_>>>(keys_.as<unsigned>(), nghost_, rt.ghost_count, rt.ghost_first, perm_.as<int>());
+  k_key_rank<<<ng, 256, 0, stream_>>>(keys_.as<unsigned>(), nghost_, rt.ghost_first, perm_.as<int>(), tag_.as<int>(),
+                                      perm_alt_.as<int>(), nlocal_);
+  hist_clean_ = true;
+}
+
+// tiled / LDS-staged keys: 64-bit (cell, tag) radix sort, then the ghost range of every cell
+void DemEngine::radix_sort_ghosts()
+{
+  const CellRanges cr = cell_ranges();
+  k_ghost_keys<<<div_up(nghost_, 256), 256, 0, stream_>>>(xr_[cur_].as<double4>(), tag_.as<int>(), nlocal_,
+                                                          nghost_, grid_, keys64_.as<unsigned long long>(),
+                                                          perm_.as<int>(), d_flags_);
+  sort_pairs_u64(sort_tmp_, sort_tmp_bytes_, keys64_.as<unsigned long long>(),
+                 keys64_alt_.as<unsigned long long>(), perm_.as<int>(), perm_alt_.as<int>(), nghost_, 64,
+                 stream_);
+  k_cell_bounds<unsigned long long><<<div_up(nghost_, 256), 256, 0, stream_>>>(
+      keys64_alt_.as<unsigned long long>(), nghost_, 32, cr.ghost_start, cr.ghost_end, CellRanges::stride);
+}
+
+// the counters of an attempt start from zero: by k_pbc_keys of this rebuild (no launch) or by a launch of their own
+void DemEngine::clear_build_counters()
+{
+  if (build_flags_clean_) h_flags_[F_NEIGH_OVER] = h_flags_[F_MAXNEIGH] = 0;
+  else set_flags3(F_NEIGH_OVER, 0, F_MAXNEIGH, 0, F_PARK_OVER, 0);
+  build_flags_clean_ = false;
+}
+
+// the kernels that park in LDS may use all 160 KB of it (set once per process)
+static void allow_full_lds_for_the_list_build()
+{
+  static bool lds_attr_set = false;
+  if (lds_attr_set) return;
+  for (const void* kernel : {reinterpret_cast<const void*>(&k_build_neigh<true>),
+                             reinterpret_cast<const void*>(&k_build_neigh_quad<4>),
+                             reinterpret_cast<const void*>(&k_build_neigh_quad<2>),
+                             reinterpret_cast<const void*>(&k_build_neigh_quad<8>)})
+    SF_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBuildLdsMax));
+  lds_attr_set = true;
+}
+
+// BuildParams, the LDS bytes and the destination word array of one attempt: the one place where "parked in LDS",
+// hist_in_place_, park_rows_ and the LDS bound are reconciled
+DemEngine::ListBuild DemEngine::list_build_params(int attempt)
+{
+  ListBuild lb;
+  BuildParams& B = lb.B;
+  B.nlocal = nlocal_;
+  B.M = M_;
+  B.Mold = max_neigh_used_;
+  B.cap = cap_;
+  B.skin_gran = gran_.style ? lskin() : -1.0;
+  B.cut_lub = lub_.enabled ? lub_.cut_global + lskin() : 0.0;
+  // fix cohesive walks a regular half list (fix_cohesive.cpp:75-77), whose criterion is the pair cutoff + skin for
+  // every pair, not ri + rj + skin: pairs enter that list exactly when LAMMPS would list them
+  if (cohe_.enabled) B.cut_lub = std::max(B.cut_lub, cutneighmax());
+  B.g = grid_;
+  B.eoff = lds_active_ ? eoff_ : nullptr;
+  B.nloc = nloc_.as<unsigned short>();
+  B.old_index = hist_indirect_ ? hist_perm_.as<int>() : nullptr;
+  B.two_copies = hist_single_ ? 0 : 1;
+  B.touch_first = touch_first_ ? 1 : 0;
+  const CellRowTables rt = cell_row_tables();
+  B.lb_own = row_tables_ ? rt.own_first : nullptr;
+  B.lb_ghost = (row_tables_ && nghost_) ? rt.ghost_first : nullptr;   // (nghost_ < 0: on the device)
+  // parked candidates in LDS (row path): as long as the rows fit; a list read in place needs them there (the scratch
+  // rows of the other form ARE the word array the new list goes into)
+  lb.parked_in_lds = row_tables_ && (hist_in_place_ || build_parks_in_lds());
+  // (parking rows: the longest row of the previous list + 8 -- a fifth of the LDS of a compute unit per block otherwise,
+  // at four waves per SIMD; an atom with more candidates than that reports F_PARK_OVER and the list is built again)
+  if (park_rows_ <= 0 || park_rows_ > M_ || attempt > 0) park_rows_ = M_;
+  B.P = park_rows_;
+  lb.lds_bytes = lb.parked_in_lds ? (size_t)park_rows_ * kBuildLdsPerSlot : 0;
+  if (lb.lds_bytes > kBuildLdsMax)
+    fail("neighbor list rows of more than %d slots do not fit the list build's LDS rows (SF_HIST_IN_PLACE=0 SF_BUILD_LDS=0 "
+         "builds such lists through memory)", (int)(kBuildLdsMax / kBuildLdsPerSlot));
+  if (lb.parked_in_lds) allow_full_lds_for_the_list_build();
+  B.old_words = hist_in_place_ ? neigh_.as<int>() : nullptr;
+  B.old_tag = hist_in_place_ ? tmpi_.as<int>() : nullptr;   // (permute_locals swapped the old tag array out into tmpi_)
+  lb.new_words = hist_in_place_ ? neigh_old_.as<int>() : neigh_.as<int>();
+  B.roots = roots_ ? 1 : 0;
+  B.gsrc = gsrc_.as<int>();
+  B.gshift = gshift_.as<double>();
+  for (int k = 0; k < 3; k++) {
+    B.inv_prd[k] = 1.0 / (boxhi_[k] - boxlo_[k]);
+    B.prd[k] = boxhi_[k] - boxlo_[k];
+  }
+  if (roots_ && cap_ > (size_t)kIdxMask) fail("more than %d atom slots per GPU: not addressable by the neighbour word", kIdxMask);
+  return lb;
+}
+
+// One of the six instantiations.  Four lanes per atom on four consecutive records (k_build_neigh_quad): single domain
+// without a ghost pass
+// (rows of full-cutoff cells -- loose beds, ~8 records -- keep four lanes busy: 405 -> 297 us on the loose 1 M bed, 60 -> 39 us
+// at 100 k grains)
+// (the 25 rows of 2-3 records of a packed bed's half-cutoff cells: two lanes, 399 -> 347-355 us at 1 M; four lanes 446)
+void DemEngine::launch_list_build(const ListBuild& lb)
+{
+  const BuildParams& B = lb.B;
+  const int lq = build_quad_set_ ? build_quad_env_ : (grid_.stencil == 1 ? 4 : 2);   // (the default follows the sort cells)
+  const bool quad = lb.parked_in_lds && !B.lb_ghost && !grid_.xslow && (lq == 2 || lq == 4 || lq == 8);
+  const CellRanges cr = cell_ranges();   // (read by k_build_neigh<false, false> alone: the row forms go by B.lb_own / B.lb_ghost)
+  auto build_quad = [&](auto lanes) {   // (128 / LQ atoms per workgroup of 128 lanes)
+    constexpr int LQ = decltype(lanes)::value;
+    k_build_neigh_quad<LQ><<<div_up(nlocal_, 128 / LQ), 128, lb.lds_bytes / LQ, stream_>>>(
+        B, xr_[cur_].as<double4>(), tag_.as<int>(), old_rows() ? numneigh_.as<int>() : nullptr, ptag_.as<int>(),
+        shear_[hist_buf_].as<double>(), lb.new_words, numneigh_old_.as<int>(), shear_[hist_buf_ ^ 1].as<double>(), d_flags_,
+        xhold_.as<double>());
+  };
+  auto build = [&](auto kernel, int* old_words) {   // (lds_bytes: 0 without parking rows in LDS)
+    kernel<<<div_up(nlocal_, 128), 128, lb.lds_bytes, stream_>>>(
+        B, xr_[cur_].as<double4>(), tag_.as<int>(), cr.own_start, cr.own_end, cr.ghost_start, cr.ghost_end,
+        perm_alt_.as<int>(), old_rows() ? numneigh_.as<int>() : nullptr, ptag_.as<int>(), shear_[hist_buf_].as<double>(),
+        lb.new_words, numneigh_old_.as<int>(), shear_[hist_buf_ ^ 1].as<double>(), d_flags_, old_words, xhold_.as<double>());
+  };
+  if (quad && lq == 2) build_quad(int_c<2>{});
+  else if (quad && lq == 8) build_quad(int_c<8>{});
+  else if (quad) build_quad(int_c<4>{});
+  else if (lb.parked_in_lds) build(k_build_neigh<true>, nullptr);
+  else if (!row_tables_) build(k_build_neigh<false, false>, neigh_old_.as<int>());
+  else build(k_build_neigh<false>, neigh_old_.as<int>());
+}
+
+// Queues the partner-slot pass behind the build and reads the build's counters meanwhile.  A ghost count that stayed on the
+// device (nghost_ < 0) arrives with them.
+DemEngine::BuildOutcome DemEngine::read_build_outcome(const ListBuild& lb)
+{
+  // the host looks at the counts (overflow, widest row) while the partner-slot pass below is already running: it
+  // needs nothing but the list, and a list that overflowed -- rare -- is built again and the pass repeated
+  flags_copy_begin();
+  // partner slots: where does the owner keep this pair?  (a partner whose owner does not list it back owns the pair)
+  k_back_slots<<<div_up(nlocal_, 128), 128, 0, stream_>>>(lb.new_words, numneigh_old_.as<int>(), nlocal_, cap_,
+                                                          roots_ ? 1 : 0, d_flags_);
+  flags_copy_wait();
+  if (nghost_ < 0) {
+    if (h_flags_[F_GHOST_OVER] || (size_t)nlocal_ + (size_t)h_flags_[F_GHOST_COUNT] > cap_)
+      return BuildOutcome::ghosts_over_capacity;
+    nghost_ = h_flags_[F_GHOST_COUNT];
+  }
+  if (h_flags_[F_NEIGH_OVER] > M_) return BuildOutcome::widen_rows;
+  if (lb.parked_in_lds && h_flags_[F_PARK_OVER] > park_rows_) return BuildOutcome::more_parking_rows;
+  return BuildOutcome::done;
+}
+
+// the list just built becomes the list of the sub-steps; the per-rebuild state is spent
+void DemEngine::adopt_new_list()
+{
   std::swap(numneigh_, numneigh_old_);
   if (hist_in_place_) std::swap(neigh_.ptr, neigh_old_.ptr);   // (the new words went into the other array)
   hist_in_place_ = false;
@@ -1795,36 +1874,17 @@ void DemEngine::bin_and_build()
   if ((hist_buf_ ^ 1) != cur_) std::swap(shear_[0].ptr, shear_[1].ptr);
   hist_indirect_ = false;   // the old rows are gone with the old list
   // (the statistics steer slow choices behind hysteresis -- history copies, slot order, v / omega prefetch, cache
-  // policy.  A list is measured whenever the last measured fractions lie within 0.08 of a band a decision switches
-  // on -- so the decisions are those of measuring EVERY list as long as a fraction does not jump a whole margin
-  // between two lists, whatever the count or the chunking of the rebuilds -- and otherwise on the first lists and
-  // every fourth one, which only refreshes numbers no decision is near; the counters keep their values in between)
-  if (nbuilds_ < 4 || (nbuilds_ & 3) == 0 || list_stats_near_a_threshold()) measure_list();
+  // policy.  A list is measured whenever the last measured fractions lie near a band a decision switches on, and
+  // otherwise on the first lists and every fourth one, which only refreshes numbers no decision is near
+  // (sf_list_policy.h, measure_this_list); the counters keep their values in between)
+  if (measure_this_list(nbuilds_, stats_near_a_band(list_stats()))) measure_list();
   max_neigh_used_ = h_flags_[F_MAXNEIGH];
   // (SF_PARK_MARGIN: the tests make the rows too few on purpose -- the F_PARK_OVER path builds the list again)
-  static const int park_margin = env_int("SF_PARK_MARGIN", 8);
-  park_rows_ = std::max(1, std::min(M_, max_neigh_used_ + park_margin));
+  park_rows_ = std::max(1, std::min(M_, max_neigh_used_ + park_margin_env_));
   have_list_ = true;   // (xhold, the positions the skin/2 check refers to, was stored by k_build_neigh)
   hist_rows_ = false;  // (the rows read_restart left were re-injected into this list)
   nbuilds_++;
   if (xcd_auto_ && xcd_countdown_ == 0) xcd_countdown_ = 3;   // the third full launch on the new list is timed per XCD
-}
-
-// true when a decision taken from the list statistics could change with the next measurement: a fraction within
-// 0.08 of the hysteresis band of the history copies (0.45 / 0.60), the slot order (0.40 / 0.50) or the v, omega
-// prefetch (0.70 / 0.85)
-bool DemEngine::list_stats_near_a_threshold() const
-{
-  const double m = 0.08;
-  if (h_flags_[F_PART_SLOTS] > 0) {
-    const double c = (double)h_flags_[F_PART_COAL] / (double)h_flags_[F_PART_SLOTS];
-    if (c > 0.45 - m && c < 0.60 + m) return true;
-  }
-  if (h_flags_[F_LIST_SLOTS] > 0) {
-    const double t = (double)h_flags_[F_LIST_TOUCH] / (double)h_flags_[F_LIST_SLOTS];
-    if ((t > 0.40 - m && t < 0.50 + m) || (t > 0.70 - m && t < 0.85 + m)) return true;
-  }
-  return false;
 }
 
 // List statistics that pick the kernel variant and the history layout (read back with the flags at the next
@@ -1863,19 +1923,14 @@ void DemEngine::measure_list()
 
 void DemEngine::choose_kernel()
 {
+  // every rule below: sf_list_policy.h
+  const ListStats s = list_stats();
   // Non-temporal policy of the row streams (sf_dem_kernels.h, NTP): what one sub-step touches against the 256 MB
-  // memory-side cache.  Records in + out 192 B, history in + out 48 B per stored copy, list words, fix arrays.
+  // memory-side cache
   {
-    const double khalf = (list_sampled_ > 0 && h_flags_[F_LIST_SLOTS] > 0)
-                             ? 0.5 * (double)h_flags_[F_LIST_SLOTS] / (double)list_sampled_ : 6.0;
-    const double copies = hist_single_ ? 1.0 : 2.0;
-    const double touched = (double)nlocal_ * (252.0 + (8.0 + 48.0 * copies) * khalf);
-    const double mall = 256.0 * 1024.0 * 1024.0;
+    const double touched = substep_bytes_touched(nlocal_, list_sampled_, h_flags_[F_LIST_SLOTS], hist_single_);
     const int before = nt_policy_;
-    if (nt_policy_env_ >= 0) nt_policy_ = nt_policy_env_;
-    else if (touched < mall) nt_policy_ = 0;
-    else if (touched < 1.4 * mall) nt_policy_ = 3;
-    else nt_policy_ = hist_single_ ? 1 : 2;
+    nt_policy_ = choose_nt_policy(touched, hist_single_, nt_policy_env_);
     if (debug_hist() && before != nt_policy_)
       fprintf(stderr, "[sedifoam_amd] a sub-step touches %.0f MB -> non-temporal policy %d\n", touched / 1048576.0,
               nt_policy_);
@@ -1885,33 +1940,21 @@ void DemEngine::choose_kernel()
   // is 1.3 % faster on full-cutoff cells and its many rebuilds 5 % (nine cell rows of ~8 candidates instead of 25 of 2-3):
   // +2.3 % on the loose 1 M bed.  Decided on the fraction of listed neighbours that touch, from the second list on (the
   // first list of a run carries no touch bits), same band as the v, omega prefetch; takes effect at the next rebuild.
-  if (h_flags_[F_LIST_SLOTS] > 0 && nbuilds_ >= 2) {
-    const double f = (double)h_flags_[F_LIST_TOUCH] / (double)h_flags_[F_LIST_SLOTS];
-    if (f < 0.70) sort_sub_ = 1;
-    else if (f > 0.85) sort_sub_ = 2;
-  }
-  if (touch_prefetch_env_ >= 0) {
-    touch_prefetch_ = touch_prefetch_env_ != 0;
-    return;
-  }
-  if (h_flags_[F_LIST_SLOTS] <= 0) return;
-  const double frac = (double)h_flags_[F_LIST_TOUCH] / (double)h_flags_[F_LIST_SLOTS];
-  // hysteresis: prefetch by touch bit below 0.70, always above 0.85
+  sort_sub_ = choose_sort_sub(sort_sub_, s, nbuilds_);
+  // v, omega prefetched by touch bit in a loose bed, always in a packed one
   const bool before = touch_prefetch_;
-  if (touch_prefetch_ && frac > 0.85) touch_prefetch_ = false;
-  else if (!touch_prefetch_ && frac < 0.70) touch_prefetch_ = true;
-  if (debug_hist() && before != touch_prefetch_)
-    fprintf(stderr, "[sedifoam_amd] %.3f of the listed neighbours touch -> v, omega %s\n", frac,
+  touch_prefetch_ = choose_touch_prefetch(touch_prefetch_, s, touch_prefetch_env_);
+  if (debug_hist() && touch_prefetch_env_ < 0 && before != touch_prefetch_)
+    fprintf(stderr, "[sedifoam_amd] %.3f of the listed neighbours touch -> v, omega %s\n", s.touching,
             touch_prefetch_ ? "prefetched by touch bit" : "always prefetched");
 }
 
 void DemEngine::rebuild_finish()
 {
   make_periodic_ghosts();
-  trigger_rearmed_ = false;
-  bin_and_build();
+  const bool trigger_rearmed = bin_and_build();
   if (overlap_) mark_boundary();
-  if (trigger_rearmed_) h_flags_[F_TRIGGER] = INT_MAX;   // (by k_back_slots, the last kernel of the list build)
+  if (trigger_rearmed) h_flags_[F_TRIGGER] = INT_MAX;   // (by k_back_slots, the last kernel of the list build)
   else reset_flag(F_TRIGGER, INT_MAX);
 }
 
