@@ -194,6 +194,13 @@ int sf_lammps_global_launches(void *ptr, long long *launches, long long *host_co
 /* measurement (tools/global_cost.py): GPU ms of one fresh evaluation of global compute `id` now, from HIP events (the
  * per-atom computes behind its c_ inputs are evaluated before the clock starts) */
 int sf_lammps_global_cost(void *ptr, const char *id, double *ms);
+/* unwrapped coordinates (the attributes xu yu zu ix iy iz of `compute property/atom`, `compute ID group displace/atom`,
+ * `compute ID group com`): the engine counts, per tag, how many box
+ * lengths the periodic wrap has taken an atom back by.  out[3 * nlocal]: ix iy iz of the owned atoms in the atom order
+ * of sf_lammps_get_local_info, so that x + ix * (boxhi - boxlo) is the unwrapped position.  One rank, no fix rigid/nve;
+ * on an engine filled through sf_dem_create_atoms the counts start with the first of these keywords or calls, which must
+ * come before the first run.  The computes are queried through sf_lammps_compute_atom / sf_lammps_compute_global */
+int sf_lammps_get_image(void *ptr, int *out);
 /* histograms (`fix ID group ave/histo Nevery Nrepeat Nfreq lo hi Nbin value ... [mode scalar|vector] [kind global|peratom|
  * local] [beyond ignore|end|extra] [ave one|running|window M] [start N] [file NAME] [overwrite] [title1|2|3 STRING]`,
  * `unfix ID`): the latest output of fix `id` -- what the last block of the fix's file holds.  *step its step, stats4 =

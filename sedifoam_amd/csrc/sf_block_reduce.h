@@ -9,7 +9,8 @@ namespace sf {
 
 // comb(c, a, b): the combination of component c (a sum, a maximum, a minimum); it is called with a compile-time c in the
 // wave tree and with c = threadIdx.x in the last step.  Components c >= nuse (uniform over the block) are left alone and
-// not stored.  Every thread of the block calls this, once per kernel (one static LDS buffer).
+// not stored.  Every thread of the block calls this, once per kernel (one static LDS buffer) -- or again with the same
+// BLOCK and NV only behind a __syncthreads() that every thread passes after the earlier call (k_global_unwrapped).
 template <int BLOCK, int NV, class Combine>
 __device__ __forceinline__ void block_reduce_store(double (&v)[NV], double* out, int nuse, Combine comb)
 {

@@ -26,4 +26,8 @@ void atom_compute_invalidate(SfLammps& L);
 long long atom_compute_launches(const SfLammps& L);
 // GPU time from HIP events of one fresh evaluation of `id` (tools/compute_atom_cost.py)
 double atom_compute_cost(SfLammps& L, const std::string& id);
+// compute displace/atom: is there one, and lammps_create_particle has made atoms with the tags d_tags[0 .. np) (device) --
+// where they are now is their reference (displace_created of sf_displace.hip calls both)
+bool atom_compute_tracks_created(const SfLammps& L);
+void atom_compute_created(SfLammps& L, const int* d_tags, int np);
 }  // namespace sf

@@ -10,7 +10,10 @@
 //   compute ID group ke/atom               1/2 m v^2
 //   compute ID group erotate/sphere/atom   1/2 (0.4 m r^2) omega^2
 //   compute ID group property/atom a1 ...  id type mass radius diameter x y z vx vy vz fx fy fz omegax omegay omegaz tqx tqy
-//                                          tqz as stored: one attribute a per-atom vector, several an array
+//                                          tqz as stored; xu yu zu ix iy iz: the unwrapped coordinates and the periodic
+//                                          image counts (sf_unmap.h).  One attribute a per-atom vector, several an array
+//   compute ID group displace/atom         dx dy dz and their length: unmap(x) - x0, x0 the unwrapped position when the
+//                                          compute was defined (of an atom created later: at its creation); DESIGN.md 17
 // The group selects the atoms that get a value; atoms outside it read 0.  Like compute pair/local (sf_contacts.hip) a
 // value is evaluated from the state AT THE MOMENT OF THE OUTPUT -- the x v omega a dump custom frame shows, the shear
 // history sf_dem_get_history returns -- with shearupdate = false, and nothing is stored back.  (LAMMPS tallies vatom inside
@@ -33,6 +36,8 @@
 #include "sf_compute_atom.h"
 #include "sf_compute_parse.h"
 #include "sf_dem_dispatch.h"
+#include "sf_displace.h"
+#include "sf_displace_parse.h"
 #include "sf_global.h"
 #include "sf_global_parse.h"
 #include "sf_handles.h"
@@ -169,11 +174,17 @@ struct PropCols {
 __global__ __launch_bounds__(256) void k_atom_property(const double4* xr, const double4* vm, const double4* om,
                                                        const double4* force, const double4* torque, const int* tag,
                                                        const int* type, const int* mask, int groupbit, PropCols C, int n,
-                                                       double* val)
+                                                       ImageView V, double* val)
 {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const bool in = (mask[i] & groupbit) != 0;
+  int im[3] = {0, 0, 0};
+  double xu[3] = {0.0, 0.0, 0.0};
+  if (V.image && in) {   // (null: no attribute of this compute needs it)
+    image_of(V, tag[i], im);
+    unmap(xr[i], im, V, xu);
+  }
   const double4 zero = make_double4(0.0, 0.0, 0.0, 0.0);
   const double4 x = in ? xr[i] : zero, v = in ? vm[i] : zero, w = in ? om[i] : zero, f = in ? force[i] : zero,
                 t = in ? torque[i] : zero;
@@ -202,17 +213,49 @@ __global__ __launch_bounds__(256) void k_atom_property(const double4* xr, const 
         case PA_OMEGAZ: o = w.z; break;
         case PA_TQX: o = t.x; break;
         case PA_TQY: o = t.y; break;
-        default: o = t.z; break;
+        case PA_TQZ: o = t.z; break;
+        case PA_XU: o = xu[0]; break;
+        case PA_YU: o = xu[1]; break;
+        case PA_ZU: o = xu[2]; break;
+        case PA_IX: o = (double)im[0]; break;
+        case PA_IY: o = (double)im[1]; break;
+        default: o = (double)im[2]; break;
       }
       val[(size_t)k * (size_t)n + i] = o;
     }
   }
 }
 
+// dx dy dz |d| of compute displace/atom: d = unmap(x) - x0[tag], each component one rounded difference
+__global__ __launch_bounds__(256) void k_atom_displace(const double4* xr, const int* tag, const int* mask, int groupbit, int n,
+                                                       ImageView V, const double* x0, int rows, double* val)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double d[3] = {0.0, 0.0, 0.0};
+  const int t = tag[i];
+  if ((mask[i] & groupbit) && t >= 0 && t < rows) {
+    int im[3];
+    double xu[3];
+    image_of(V, t, im);
+    unmap(xr[i], im, V, xu);
+    const double* r = x0 + 3 * (size_t)t;
+#pragma unroll
+    for (int k = 0; k < 3; k++) d[k] = sub_rn(xu[k], r[k]);
+  }
+  const size_t N = (size_t)n;
+  val[i] = d[0];
+  val[N + i] = d[1];
+  val[2 * N + i] = d[2];
+  val[3 * N + i] = length_rn(d[0], d[1], d[2]);
+}
+
 // ---- host side ----
 
-enum Kind { K_STRESS, K_CONTACT, K_KE, K_EROTATE, K_PROPERTY };
-const char* const kStyleName[5] = {"stress/atom", "contact/atom", "ke/atom", "erotate/sphere/atom", "property/atom"};
+enum Kind { K_STRESS, K_CONTACT, K_KE, K_EROTATE, K_PROPERTY, K_DISPLACE };
+constexpr int kNumKinds = 6;
+const char* const kStyleName[kNumKinds] = {"stress/atom", "contact/atom", "ke/atom", "erotate/sphere/atom", "property/atom",
+                                           "displace/atom"};
 
 struct Grown {   // device scratch, grown geometrically (no allocation per frame once it has grown)
   void* p = nullptr;
@@ -241,11 +284,20 @@ struct AtomCompute {
   int groupbit = 1;
   bool ke = true, pair = true;
   std::vector<int> attrs;   // K_PROPERTY
+  RefTable ref;             // K_DISPLACE: the reference positions, by tag
   Grown val;
   // what the buffer was made at (-1: nothing)
   long long step = -1, nbuilds = -1;
   int nlocal = -1;
-  int ncols() const { return kind == K_STRESS ? 6 : (kind == K_PROPERTY ? (int)attrs.size() : 1); }
+  int ncols() const { return kind == K_STRESS ? 6 : (kind == K_PROPERTY ? (int)attrs.size() : (kind == K_DISPLACE ? 4 : 1)); }
+  bool needs_image() const
+  {
+    if (kind == K_DISPLACE) return true;
+    for (int a : attrs)
+      if (kind == K_PROPERTY && prop_attr_needs_image(a)) return true;
+    return false;
+  }
+  std::string who() const;
 };
 
 struct AtomSet {
@@ -258,6 +310,8 @@ struct AtomSet {
     return nullptr;
   }
 };
+
+std::string AtomCompute::who() const { return std::string("compute ") + kStyleName[kind]; }
 
 AtomSet* set_of(const SfLammps& L) { return static_cast<AtomSet*>(L.atom_computes); }
 AtomSet& ensure_set(SfLammps& L)
@@ -304,8 +358,14 @@ void evaluate(SfLammps& L, AtomSet& T, AtomCompute& c)
       PropCols C{};
       C.n = (int)c.attrs.size();
       for (int k = 0; k < C.n; k++) C.a[k] = c.attrs[k];
+      ImageView V{};   // (image = nullptr: not needed)
+      if (c.needs_image()) V = image_view(L, c.who().c_str());
       k_atom_property<<<nb, 256, 0, st>>>(e.d_xr(), e.d_vm(), e.d_om(), e.d_force(), e.d_torque(), e.d_tag(), e.d_type(),
-                                          e.d_mask(), c.groupbit, C, n, val);
+                                          e.d_mask(), c.groupbit, C, n, V, val);
+    } else if (c.kind == K_DISPLACE) {
+      const ImageView V = image_view(L, c.who().c_str());
+      c.ref.fit(e);
+      k_atom_displace<<<nb, 256, 0, st>>>(e.d_xr(), e.d_tag(), e.d_mask(), c.groupbit, n, V, c.ref.x0, (int)c.ref.rows, val);
     } else {
       DemPtrs P;
       StepParams S;
@@ -352,7 +412,7 @@ void atom_compute_define(SfLammps& L, const std::vector<std::string>& w)
   auto c = std::make_unique<AtomCompute>();
   c->id = w[1];
   c->groupbit = L.eng.group_bit(w[2]);
-  for (int k = 0; k < 5; k++)
+  for (int k = 0; k < kNumKinds; k++)
     if (w[3] == kStyleName[k]) c->kind = (Kind)k;
   if (c->kind == K_STRESS) {
     const std::string err = parse_stress_keywords(w, 4, &c->ke, &c->pair);
@@ -360,9 +420,16 @@ void atom_compute_define(SfLammps& L, const std::vector<std::string>& w)
   } else if (c->kind == K_PROPERTY) {
     const std::string err = parse_property_atom(w, &c->attrs);
     if (!err.empty()) fail("%s", err.c_str());
+  } else if (c->kind == K_DISPLACE) {
+    const std::string err = parse_displace_atom(w);
+    if (!err.empty()) fail("%s", err.c_str());
   } else if (w.size() != 4)
     fail("Illegal compute %s command", w[3].c_str());
   refuse_unsupported(L, c->kind);
+  if (c->needs_image()) {
+    const ImageView V = image_view(L, c->who().c_str());   // (refused where image counts cannot be kept; makes the table)
+    if (c->kind == K_DISPLACE) ref_set_all(L, c->ref, V);
+  }
   ensure_set(L).computes.push_back(std::move(c));
 }
 
@@ -410,6 +477,22 @@ void atom_compute_invalidate(SfLammps& L)
   global_invalidate(L);
   if (AtomSet* T = set_of(L))
     for (auto& c : T->computes) c->step = -1;
+}
+
+bool atom_compute_tracks_created(const SfLammps& L)
+{
+  if (const AtomSet* T = set_of(L))
+    for (const auto& c : T->computes)
+      if (c->kind == K_DISPLACE) return true;
+  return false;
+}
+
+void atom_compute_created(SfLammps& L, const int* d_tags, int np)
+{
+  AtomSet* T = set_of(L);
+  if (!T) return;
+  for (auto& c : T->computes)
+    if (c->kind == K_DISPLACE) ref_set_tags(L, c->ref, image_view(L, c->who().c_str()), d_tags, np);
 }
 
 long long atom_compute_launches(const SfLammps& L)

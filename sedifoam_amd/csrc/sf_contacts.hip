@@ -347,7 +347,8 @@ bool compute_command(SfLammps& L, const std::vector<std::string>& w)
   if (style != "pair/local" && style != "gran/local" && !per_atom && !global)
     fail("Invalid compute style %s (this engine has compute pair/local, also under the name gran/local, the per-atom "
          "computes stress/atom, contact/atom, ke/atom, erotate/sphere/atom, property/atom and chunk/atom, and the global "
-         "computes reduce, ke and erotate/sphere)", style.c_str());
+         "computes reduce, ke and erotate/sphere; on unwrapped coordinates the per-atom compute displace/atom and the global "
+         "compute com)", style.c_str());
   Compute c;
   c.id = w[1];
   c.groupbit = L.eng.group_bit(w[2]);

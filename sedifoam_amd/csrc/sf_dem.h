@@ -579,6 +579,20 @@ class DemEngine {
   int* d_mask() const { return mask_.as<int>(); }   // group bits ([3P] atom->mask)
   int* d_foamCpuId() const { return foamCpuId_.as<int>(); }
   int max_tag() const { return max_tag_; }
+  // ---- periodic image counts: how many box lengths k_pbc_keys has taken an atom back by, three
+  // ints per TAG (row tag of a table that grows with max_tag_; a new tag reads 0).  By tag and not per atom: the table
+  // stays out of the re-sort's permutation, the migration record and the restart file.  Without the table (the raw
+  // sf_dem_* path) k_pbc_keys gets a null pointer and does what it did before.
+  // true: the table exists (now or already).  false: it does not and it is too late to start one -- k_pbc_keys has
+  // wrapped a periodic dimension without counting, so a count from here on would not be LAMMPS' count from the start
+  bool images_enable();
+  bool images_on() const { return image_ != nullptr; }
+  const int* d_image();                         // (fitted to max_tag_ first)
+  int image_rows() const { return (int)image_rows_; }
+  void box_lengths(double prd[3]) const
+  {
+    for (int k = 0; k < 3; k++) prd[k] = boxhi_[k] - boxlo_[k];   // (k_pbc_keys' own prd)
+  }
 
   long long nbuilds() const { return nbuilds_; }
   long long nsteps() const { return nsteps_; }
@@ -885,6 +899,10 @@ private:
   // which layout cell_start_ holds: set by rebuild_sort, consumed by make_periodic_ghosts (may the count stay on the
   // device?), sort_ghosts_into_cells, list_build_params and launch_list_build
   bool row_tables_ = false;
+  int* image_ = nullptr;      // [image_rows_][3], row = tag: see images_enable()
+  size_t image_rows_ = 0;
+  bool uncounted_wraps_ = false;   // k_pbc_keys has wrapped a periodic dimension while there was no table
+  void images_fit();          // rows for every tag up to max_tag_; new rows are zero
   int* tagmap_ = nullptr;
   size_t tagmap_alloc_ = 0;
   long long order_version_ = 0, tagmap_builds_ = -1;   // the tag -> index table is rebuilt when the atom order changed

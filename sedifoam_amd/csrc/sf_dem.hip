@@ -182,6 +182,7 @@ DemEngine::~DemEngine()
   if (stage_idx_) (void)hipFree(stage_idx_);
   if (eoff_) (void)hipFree(eoff_);
   if (tagmap_) (void)hipFree(tagmap_);
+  if (image_) (void)hipFree(image_);
   for (IoBuf& b : io_d_)
     if (b.p) (void)hipFree(b.p);
   for (IoBuf& b : io_i_)
@@ -1465,8 +1466,10 @@ void DemEngine::rebuild_sort()
     SF_HIP(hipMemsetAsync(rt.ghost_count, 0, sizeof(int) * cell_alloc_, stream_));
   }
   hist_clean_ = false;   // (until the kernels below have run: an error in between leaves it dirty)
+  if (image_) images_fit();
+  else if (pb.wrap[0] || pb.wrap[1] || pb.wrap[2]) uncounted_wraps_ = true;
   k_pbc_keys<<<nb, 256, 0, stream_>>>(xr_[cur_].as<double4>(), nlocal_, pb, grid_, keys_.as<unsigned>(),
-                                      perm_.as<int>(), d_flags_, count);
+                                      perm_.as<int>(), d_flags_, count, tag_.as<int>(), image_, (int)image_rows_);
   build_flags_clean_ = true;   // (F_NEIGH_OVER, F_MAXNEIGH zeroed by that kernel: the first list build needs no reset launch)
   if (row_tables_) {
     const int ne = grid_.nbins + 1;
@@ -2388,6 +2391,38 @@ void DemEngine::put_local_info(int n, const double* fdrag, const int* foamCpuId,
     reset_flag(F_LOST, 0);
     fail("lammps_put_local_info: incoming tag not owned by this rank");
   }
+}
+
+// ---- periodic image counts (sf_dem.h) ----
+bool DemEngine::images_enable()
+{
+  if (image_) return true;
+  if (uncounted_wraps_) return false;
+  images_fit();
+  return true;
+}
+
+void DemEngine::images_fit()
+{
+  const size_t need = (size_t)max_tag_ + 1;
+  if (image_ && need <= image_rows_) return;
+  const size_t rows = need + need / 4 + 1024;
+  int* p = nullptr;
+  SF_HIP(hipMalloc(&p, sizeof(int) * 3 * rows));
+  SF_HIP(hipMemsetAsync(p, 0, sizeof(int) * 3 * rows, stream_));
+  if (image_) {
+    SF_HIP(hipMemcpyAsync(p, image_, sizeof(int) * 3 * image_rows_, hipMemcpyDeviceToDevice, stream_));
+    sync();   // (a kernel queued on the stream may still read the old table)
+    SF_HIP(hipFree(image_));
+  }
+  image_ = p;
+  image_rows_ = rows;
+}
+
+const int* DemEngine::d_image()
+{
+  if (image_) images_fit();
+  return image_;
 }
 
 long long DemEngine::npairs_full()

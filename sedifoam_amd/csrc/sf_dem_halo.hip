@@ -1167,6 +1167,17 @@ long long DemEngine::migrate_count3()
 // ------------------------------------------------------------------------------------------------
 // lammps_create_particle / lammps_delete_particle (library.cpp:406-621)
 // ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_image_zero(const int* tag, int n, int* image, int image_rows)
+{
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const int t = tag[k];
+  if (t < 0 || t >= image_rows) return;
+  image[3 * (size_t)t] = 0;
+  image[3 * (size_t)t + 1] = 0;
+  image[3 * (size_t)t + 2] = 0;
+}
+
 void DemEngine::create_particles(int np, const double* pos, const double* tag, double diameter, double rho, int type,
                                  const double* vel)
 {
@@ -1227,6 +1238,10 @@ void DemEngine::create_particles(int np, const double* pos, const double* tag, d
     std::vector<double> iv(np, extra_init_[r]);
     up(extra_, iv.data(), sizeof(double) * np, sizeof(double) * ((size_t)r * cap_ + nlocal_));
     sync();
+  }
+  if (image_) {   // a created atom starts in image 0, whatever an earlier holder of its tag had counted
+    images_fit();
+    k_image_zero<<<div_up(np, 256), 256, 0, stream_>>>(tag_.as<int>() + nlocal_, np, image_, (int)image_rows_);
   }
   sync();
   nlocal_ += np;

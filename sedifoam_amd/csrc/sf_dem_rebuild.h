@@ -279,24 +279,30 @@ __device__ __forceinline__ void key_runs(const unsigned key, int& head, int& len
 
 // [3P] Domain::pbc for owned atoms + bin key
 // (count: the counting sort's histogram, filled in the same pass; nullptr on the radix-sort path)
+// (image: the periodic image counts, row tag[i] of [image_rows][3], or nullptr: -1 where a box length was added, +1 where
+// one was taken off -- this kernel moves an atom by at most one box length per dimension)
 __global__ __launch_bounds__(256) void k_pbc_keys(double4* xr, int nlocal, PbcParams pb, BinGrid g,
-                                                  unsigned* keys, int* perm, int* flags, int* count)
+                                                  unsigned* keys, int* perm, int* flags, int* count, const int* tag,
+                                                  int* image, int image_rows)
 {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nlocal) return;
   double4 x = xr[i];
   double c[3] = {x.x, x.y, x.z};
+  int up[3] = {0, 0, 0};
   bool moved = false;
   for (int k = 0; k < 3; k++) {
     if (!pb.wrap[k]) continue;
     const double prd = pb.hi[k] - pb.lo[k];
     if (c[k] < pb.lo[k]) {
       c[k] += prd;
+      up[k]--;
       moved = true;
     }
     if (c[k] >= pb.hi[k]) {
       c[k] -= prd;
       if (c[k] < pb.lo[k]) c[k] = pb.lo[k];
+      up[k]++;
       moved = true;
     }
   }
@@ -305,6 +311,12 @@ __global__ __launch_bounds__(256) void k_pbc_keys(double4* xr, int nlocal, PbcPa
     x.y = c[1];
     x.z = c[2];
     xr[i] = x;
+    if (image) {
+      const int t = tag[i];
+      if (t >= 0 && t < image_rows)
+        for (int k = 0; k < 3; k++)
+          if (up[k]) image[3 * (size_t)t + k] += up[k];
+    }
   }
   int lost = 0;
   const unsigned key = (unsigned)bin_of(x, g, lost);

@@ -3,6 +3,9 @@
 //       per-atom inputs over the atoms of the group, the columns of a compute pair/local over all of its rows; one input a
 //       global scalar, several a global vector
 //   compute ID group ke | erotate/sphere      the group sums of the terms of ke/atom and erotate/sphere/atom (sf_atom_terms.h)
+//   compute ID group com                      sum m unmap(x) / sum m over the group ([3P] Group::xcm), three values
+//                                             (a mean squared displacement is compute reduce avesq
+//                                             over the columns of a compute displace/atom)
 //   fix ID group ave/time Nevery Nrepeat Nfreq c_ID c_ID[k] ... [ave one|running|window M] [start N] [file F] [overwrite]
 //       [format S] [title1 S] [title2 S]       time averages of global values, one line per Nfreq steps
 // A value is evaluated from the state AT THE MOMENT OF THE OUTPUT, like a dump frame, and stores nothing back into the run.
@@ -16,6 +19,10 @@
 //   k_global_fold    one block folds the partial rows in a fixed order, divides ave / avesq by the count (a count column of
 //                    the same launch, or the row count), stores the values, and adds them into the accumulators of the fix
 //                    ave/time samples due at this step
+//   k_global_unwrapped   compute com: ONE launch.  A group atom loads its two records, mask and tag and gathers its image
+//                    counts by tag; the sums stay in registers, go through the same wave64 tree and LDS step into one partial row per block, and the block
+//                    that arrives last (an integer ticket behind an agent-scope release) folds the rows in row order and
+//                    stores the values
 // More than 16 columns take more launches; atom columns and row columns have different element counts and go in separate
 // launches.  No floating-point atomics, no scratch: the same state gives the same bits, and which thread adds which element
 // does not depend on the other columns of the launch.  Nothing is copied to the host before an output step, a thermo line
@@ -37,6 +44,8 @@
 #include "sf_chunk.h"
 #include "sf_compute_atom.h"
 #include "sf_contacts.h"
+#include "sf_displace.h"
+#include "sf_displace_parse.h"
 #include "sf_gather_col.h"
 #include "sf_global.h"
 #include "sf_global_parse.h"
@@ -185,10 +194,81 @@ __global__ __launch_bounds__(64) void k_global_acc(GAccOnly A)
   *dst += *src;
 }
 
+// ---- compute com ----
+
+constexpr int kUCols = 4;   // sum m xu, m yu, m zu, m
+struct UArgs {
+  const double4* xr;
+  const double4* vm;
+  const int* mask;
+  const int* tag;
+  int groupbit;
+  ImageView V;
+};
+
+// grid: the element count alone decides it (at least one block, which then stores the zeros of an empty bed); partial:
+// [gridDim.x][kUCols]; ticket: zero before the launch and again after it; out: three values
+__global__ __launch_bounds__(kGBlock) void k_global_unwrapped(UArgs A, long long n, double* partial, unsigned* ticket,
+                                                              double* out)
+{
+  __shared__ int last;
+  __shared__ double folded[kUCols];
+  double acc[kUCols] = {0.0, 0.0, 0.0, 0.0};
+  const long long stride = (long long)gridDim.x * kGBlock;
+  for (long long i = (long long)blockIdx.x * kGBlock + threadIdx.x; i < n; i += stride) {
+    if (!(A.mask[i] & A.groupbit)) continue;
+    int im[3];
+    double xu[3];
+    image_of(A.V, A.tag[i], im);
+    unmap(A.xr[i], im, A.V, xu);
+    const double m = A.vm[i].w;
+    acc[0] += xu[0] * m;
+    acc[1] += xu[1] * m;
+    acc[2] += xu[2] * m;
+    acc[3] += m;
+  }
+  auto add = [](int, double a, double b) { return a + b; };
+  block_reduce_store<kGBlock, kUCols>(acc, partial + (size_t)kUCols * blockIdx.x, kUCols, add);
+  // this block's row is published before its ticket is drawn: every storing wave's stores have left, then one agent-scope
+  // release (the per-XCD L2s are not coherent), then the relaxed add; the block that draws the last ticket acquires once
+  // and reads every row with plain loads.  (The waits written out next to the fences repeat what the fences are meant to
+  // emit: the compiler has been seen to drop a fence's own wait where it believes no store is in flight, and the ticket
+  // must never overtake the row.)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned drawn = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last = drawn == gridDim.x - 1 ? 1 : 0;
+    if (last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+  }
+  __syncthreads();
+  if (!last) return;
+  // the fold: thread t adds rows t, t + 256, ... in that order, then the same tree -- which block does it changes nothing.
+  // (The second block_reduce_store of this kernel, the same instantiation and so the same LDS rows as the first: the two
+  // barriers above lie between the first call's reads of those rows and this call's writes -- sf_block_reduce.h.)
+  double v[kUCols] = {0.0, 0.0, 0.0, 0.0};
+  for (int b = threadIdx.x; b < (int)gridDim.x; b += kGBlock)
+#pragma unroll
+    for (int q = 0; q < kUCols; q++) v[q] += partial[(size_t)kUCols * b + q];
+  block_reduce_store<kGBlock, kUCols>(v, folded, kUCols, add);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double m = folded[3];
+    for (int q = 0; q < 3; q++) out[q] = m > 0.0 ? folded[q] / m : 0.0;   // (a group of no atoms: zeros)
+    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 // ---- host side ----
 
-enum GKind { G_REDUCE, G_KE, G_EROTATE };
-const char* const kStyleName[3] = {"reduce", "ke", "erotate/sphere"};
+enum GKind { G_REDUCE, G_KE, G_EROTATE, G_COM };
+constexpr int kNumGKinds = 4;
+const char* const kStyleName[kNumGKinds] = {"reduce", "ke", "erotate/sphere", "com"};
 
 struct GlobalCompute {
   std::string id;
@@ -200,8 +280,9 @@ struct GlobalCompute {
   // what the values were made at (-1: nothing)
   long long step = -1, nbuilds = -1;
   int nlocal = -1;
-  bool is_vector() const { return kind == G_REDUCE && S.inputs.size() > 1; }
-  bool extensive() const { return kind != G_REDUCE || S.mode == GM_SUM || S.mode == GM_SUMSQ; }
+  bool unwrapped() const { return kind == G_COM; }
+  bool is_vector() const { return unwrapped() || (kind == G_REDUCE && S.inputs.size() > 1); }
+  bool extensive() const { return !unwrapped() && (kind != G_REDUCE || S.mode == GM_SUM || S.mode == GM_SUMSQ); }
 };
 
 struct AveTimeFix : AveFixState {
@@ -219,12 +300,14 @@ struct GlobalSet {
   double* pool = nullptr;
   std::vector<char> used = std::vector<char>(kPool, 0);
   double* partial = nullptr;   // [kGMaxBlocks][kGCols]
+  unsigned* ticket = nullptr;  // k_global_unwrapped: zero between launches
   double* h_buf = nullptr;     // pinned [kAveTimeMaxValues]
   long long launches = 0, host_copies = 0;
   ~GlobalSet()
   {
     if (pool) (void)hipFree(pool);
     if (partial) (void)hipFree(partial);
+    if (ticket) (void)hipFree(ticket);
     if (h_buf) (void)hipHostFree(h_buf);
   }
   GlobalCompute* find(const std::string& id)
@@ -240,6 +323,8 @@ struct GlobalSet {
     SF_HIP(hipMalloc(&pool, sizeof(double) * kPool));
     SF_HIP(hipMemsetAsync(pool, 0, sizeof(double) * kPool, st));
     SF_HIP(hipMalloc(&partial, sizeof(double) * kGMaxBlocks * kGCols));
+    SF_HIP(hipMalloc(&ticket, sizeof(unsigned)));
+    SF_HIP(hipMemsetAsync(ticket, 0, sizeof(unsigned), st));
     SF_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_buf), sizeof(double) * kAveTimeMaxValues));
   }
   int take(int n)   // n consecutive doubles of the pool, first fit
@@ -408,6 +493,19 @@ void launch_late_acc(SfLammps& L, GlobalSet& G, const std::vector<std::pair<cons
   }
 }
 
+// compute com: one launch of k_global_unwrapped over the owned atoms
+void evaluate_unwrapped(SfLammps& L, GlobalSet& G, GlobalCompute& c)
+{
+  const ImageView V = image_view(L, who_of(c).c_str());
+  DemEngine& e = L.eng;
+  const long long n = e.nlocal();
+  const int nb = (int)std::max<long long>(1, std::min<long long>(kGMaxBlocks, (n + kGBlock - 1) / kGBlock));
+  const UArgs A{e.d_xr(), e.d_vm(), e.d_mask(), e.d_tag(), c.groupbit, V};
+  k_global_unwrapped<<<nb, kGBlock, 0, e.stream()>>>(A, n, G.partial, G.ticket, G.pool + c.slot);
+  SF_HIP(hipGetLastError());
+  G.launches++;
+}
+
 // Every compute of `want` that is stale is evaluated, once; `accs`: the additions of the fix samples due now, carried by
 // the fold launches of the values they name (or by k_global_acc where the value was evaluated at this step before)
 void evaluate(SfLammps& L, GlobalSet& G, const std::vector<GlobalCompute*>& want, const std::vector<AccReq>& accs)
@@ -429,6 +527,12 @@ void evaluate(SfLammps& L, GlobalSet& G, const std::vector<GlobalCompute*>& want
   for (const AccReq& a : accs)
     if (std::find(stale.begin(), stale.end(), a.c) == stale.end()) late.push_back({G.pool + a.c->slot + a.value, a.dst});
   for (GlobalCompute* c : stale) {
+    if (c->unwrapped()) {   // (launches of their own; the samples of the fixes are added behind them)
+      evaluate_unwrapped(L, G, *c);
+      for (const AccReq& a : accs)
+        if (a.c == c) late.push_back({G.pool + c->slot + a.value, a.dst});
+      continue;
+    }
     for (int j = 0; j < c->nvalues; j++) {
       PlanCol pc;
       pc.out = G.pool + c->slot + j;
@@ -619,7 +723,7 @@ void global_compute_define(SfLammps& L, const std::vector<std::string>& w)
   auto c = std::make_unique<GlobalCompute>();
   c->id = w[1];
   c->groupbit = L.eng.group_bit(w[2]);
-  for (int k = 0; k < 3; k++)
+  for (int k = 0; k < kNumGKinds; k++)
     if (w[3] == kStyleName[k]) c->kind = (GKind)k;
   refuse_decomposed(L, who_of(*c).c_str());
   if (c->kind == G_REDUCE) {
@@ -627,9 +731,13 @@ void global_compute_define(SfLammps& L, const std::vector<std::string>& w)
     for (const ReduceInput& in : c->S.inputs)
       if (in.attr == AA_COMPUTE) check_reduce_input(L, in);
     c->nvalues = (int)c->S.inputs.size();
+  } else if (c->kind == G_COM) {
+    fail_if(parse_com(w));
+    c->nvalues = 3;
   } else if (w.size() != 4)
     fail("Illegal compute %s command", w[3].c_str());
   GlobalSet& G = ensure_set(L);
+  if (c->unwrapped()) (void)image_view(L, who_of(*c).c_str());   // (refused where image counts cannot be kept; makes the table)
   c->slot = G.take(c->nvalues);
   G.computes.push_back(std::move(c));
 }

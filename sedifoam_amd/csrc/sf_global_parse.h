@@ -75,16 +75,22 @@ inline std::string parse_reduce(const std::vector<std::string>& w, ReduceSpec* o
 
 enum PropAttr {
   PA_ID, PA_TYPE, PA_MASS, PA_RADIUS, PA_DIAMETER, PA_X, PA_Y, PA_Z, PA_VX, PA_VY, PA_VZ, PA_FX, PA_FY, PA_FZ, PA_OMEGAX,
-  PA_OMEGAY, PA_OMEGAZ, PA_TQX, PA_TQY, PA_TQZ, PA_COUNT
+  PA_OMEGAY, PA_OMEGAZ, PA_TQX, PA_TQY, PA_TQZ,
+  PA_COUNT,   // the attributes a state record holds as stored
+  // derived from the record and the periodic image counts (sf_unmap.h): unwrapped coordinates, and the counts themselves
+  PA_XU = PA_COUNT, PA_YU, PA_ZU, PA_IX, PA_IY, PA_IZ,
+  PA_COUNT_ALL
 };
 constexpr int kPropMaxAttrs = 24;
 
 inline const char* prop_attr_name(int a)
 {
-  static const char* const names[PA_COUNT] = {"id", "type", "mass", "radius", "diameter", "x", "y", "z", "vx", "vy",
-                                              "vz", "fx", "fy", "fz", "omegax", "omegay", "omegaz", "tqx", "tqy", "tqz"};
-  return a >= 0 && a < PA_COUNT ? names[a] : "";
+  static const char* const names[PA_COUNT_ALL] = {"id", "type", "mass", "radius", "diameter", "x", "y", "z", "vx", "vy",
+                                                  "vz", "fx", "fy", "fz", "omegax", "omegay", "omegaz", "tqx", "tqy", "tqz",
+                                                  "xu", "yu", "zu", "ix", "iy", "iz"};
+  return a >= 0 && a < PA_COUNT_ALL ? names[a] : "";
 }
+inline bool prop_attr_needs_image(int a) { return a >= PA_XU && a <= PA_IZ; }
 
 // w = compute ID group property/atom a1 ...
 inline std::string parse_property_atom(const std::vector<std::string>& w, std::vector<int>* attrs)
@@ -93,7 +99,7 @@ inline std::string parse_property_atom(const std::vector<std::string>& w, std::v
   attrs->clear();
   for (size_t k = 4; k < w.size(); k++) {
     int a = -1;
-    for (int q = 0; q < PA_COUNT; q++)
+    for (int q = 0; q < PA_COUNT_ALL; q++)
       if (w[k] == prop_attr_name(q)) a = q;
     if (a < 0) return "Invalid keyword in compute property/atom command: " + w[k];
     if ((int)attrs->size() >= kPropMaxAttrs) return "compute property/atom: more than 24 attributes";

@@ -51,8 +51,13 @@ struct SfLammps {
   // the fix ave/histo commands, their device counters and files (sf_histo.hip); opaque like halo
   void* histos = nullptr;
   void (*histos_delete)(void*) = nullptr;
+  // the device scratch of the image-count query and of the tags lammps_create_particle tells the displacement computes about
+  // (sf_displace.hip); opaque like halo
+  void* displace = nullptr;
+  void (*displace_delete)(void*) = nullptr;
   ~SfLammps()
   {
+    if (displace && displace_delete) displace_delete(displace);
     if (restart && restart_delete) restart_delete(restart);
     if (thermo && thermo_delete) thermo_delete(thermo);   // (closes the log and screen files)
     if (dumps && dumps_delete) dumps_delete(dumps);   // (drains the writer: the frames are in their files)

@@ -24,6 +24,7 @@
 #include "sf_global.h"
 #include "sf_histo.h"
 #include "sf_restart.h"
+#include "sf_displace.h"
 #include "sf_rigid.h"
 #include "sf_roctx.h"
 #include "sf_thermo.h"
@@ -280,6 +281,8 @@ void read_data(SfLammps& L, const std::string& path, bool molecules = false)
   }
   L.eng.create_atoms((int)tag.size(), x.data(), nullptr, nullptr, diam.data(), dens.data(), tag.data(),
                      type.data());
+  // (the first atoms of a script's engine on one rank: periodic images are counted from here on, as LAMMPS counts them)
+  if (L.world_size == 1 && !L.decomposed) (void)L.eng.images_enable();
   if (molecules) {
     if (L.world_size > 1) sf::fail("read_data ... fix ID NULL Molecules: one rank only (fix rigid/nve)");
     if (mol_tag.size() != tag.size()) sf::fail("read_data: the Molecules section does not list every atom");
@@ -316,6 +319,8 @@ void read_restart(SfLammps& L, const std::string& path)
   } else
     for (size_t i = 0; i < n; i++) keep.push_back((int)i);
   L.eng.restart_unpack(d, keep);
+  // (image counts are not in the file: they start at zero -- DESIGN.md section 10, "Not saved")
+  if (L.world_size == 1 && !L.decomposed) (void)L.eng.images_enable();
   sf::restart_set_pending_walls(L, std::move(d.walls));
 }
 
@@ -925,7 +930,9 @@ int sf_lammps_create_particle(void* ptr, int npAdd, const double* position, cons
   SfLammps* L = H(ptr);
   if (L->eng.rigid_on()) sf::fail("lammps_create_particle: not while fix rigid/nve exists (its bodies are fixed sets of atoms)");
   sf::atom_compute_invalidate(*L);
+  if (L->world_size == 1 && !L->decomposed && !L->eng.decomposed()) (void)L->eng.images_enable();
   L->eng.create_particles(npAdd, position, tag, diameter, rho, type, vel);
+  sf::displace_created(*L, tag, npAdd);   // (the displacement computes: the new atoms' reference is where they are now)
   if (L->decomposed) {   // library.cpp:470-473 (collective: every rank calls, possibly with npAdd = 0)
     recount_atoms(*L);
     L->pending_rebuild = true;

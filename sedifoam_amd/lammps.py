@@ -260,6 +260,17 @@ class Lammps:
         check(self.L.sf_lammps_global_cost(self.ptr, str(cid).encode(), C.byref(ms)))
         return ms.value
 
+    def images(self):
+        """ix iy iz of the owned atoms, (n, 3) int32 in the atom order of get_local_info(): how many box lengths the
+        periodic wrap has taken each atom back by, so that x + images() * (boxhi - boxlo) is the unwrapped position (the
+        xu yu zu of compute property/atom).  One rank, no fix rigid/nve; on an engine filled through
+        create_atoms the counting starts with the first call or keyword that needs it, which must come before the first
+        run"""
+        n = self.get_local_n()
+        out = np.zeros((n, 3), np.int32)
+        check(self.L.sf_lammps_get_image(self.ptr, _p(out)))
+        return out
+
     def ave_histo(self, fid):
         """the latest output of `fix fid group ave/histo ...`: dict(step, nbins, total, missing, min, max, coord[nbins],
         count[nbins], frac[nbins] (count / total, 0 when total is 0)) -- what the last block of the fix's file holds.  An
