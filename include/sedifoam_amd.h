@@ -259,6 +259,12 @@ int sf_dem_get_rebuild_profile(void *ptr, long long *rebuilds, double *ms);
 int sf_dem_get_forces(void *ptr, double *f, double *torque, double *omega, int *tag);
 /* touching pairs (tag_i < tag_j, shear oriented i->j) ; returns count or <0 */
 long long sf_dem_get_history(void *ptr, long long max, int *tag_i, int *tag_j, double *shear);
+/* every word of the full list of the owned atoms, in no particular order: owner tag, neighbour tag, which periodic image of
+ * the neighbour (sx, sy, sz in {-1,0,1}; 0 0 0: the atom itself), bit 0 of flags = touch bit, bit 1 = this side stores the
+ * pair's history.  Returns the number of words (may exceed max; only max are written) or < 0.  Single domain only. */
+long long sf_dem_get_neighbors(void *ptr, long long max, int *tag_i, int *tag_j, int *image /*3 per word*/, int *flags);
+/* the positions the current list was built from (the rows the skin/2 check refers to), AoS 3n in engine order, with tags */
+int sf_dem_get_build_positions(void *ptr, double *x, int *tag);
 /* per-atom wall shear of wall fix w, AoS 3n in engine order */
 int sf_dem_get_wall_shear(void *ptr, int w, double *shear);
 

@@ -343,6 +343,10 @@ static void bin_atoms(orc_dem *d, bingrid *g)
     }
     double len = hi - lo;
     int n = (int)(len / cut);
+    /* one cell fewer when the cells fill the length to within rounding: a cell exactly as wide as the cutoff lets the
+     * truncation of (x - lo) * inv, inv rounded, put two atoms that are one cutoff apart two cells apart (the engine's
+     * compute_grid has the same guard) */
+    if (n > 1 && len <= (double)n * cut * (1.0 + 0x1p-40)) n--;
     if (n < 1) n = 1;
     if (n > 1024) n = 1024;
     g->lo[k] = lo;

@@ -139,6 +139,8 @@ _SIGS = {
     "sf_dem_get_rebuild_profile": (C.c_int, [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
     "sf_dem_get_forces": (C.c_int, [vp, dp, dp, dp, ip]),
     "sf_dem_get_history": (C.c_longlong, [vp, C.c_longlong, ip, ip, dp]),
+    "sf_dem_get_neighbors": (C.c_longlong, [vp, C.c_longlong, ip, ip, ip, ip]),
+    "sf_dem_get_build_positions": (C.c_int, [vp, dp, ip]),
     "sf_dem_get_wall_shear": (C.c_int, [vp, C.c_int, dp]),
     "sf_dem_set_subdomain": (C.c_int, [vp, C.c_int, C.c_int, C.c_double, C.c_double]),
     "sf_dem_setup": (C.c_int, [vp]),

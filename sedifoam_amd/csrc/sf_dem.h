@@ -443,6 +443,10 @@ class DemEngine {
   void put_local_info(int n, const double* fdrag, const int* foamCpuId, const int* tagIn);
   void get_forces(double* f, double* torque, double* omega, int* tag);
   long long get_history(long long max, int* tag_i, int* tag_j, double* shear);
+  // read-only views of the list as it stands (single domain): every word as (owner tag, neighbour tag, image, flags), and
+  // the positions the list was built from
+  long long get_neighbors(long long max, int* tag_i, int* tag_j, int* image, int* flags);
+  void get_build_positions(double* x, int* tag);
   void get_wall_shear(int w, double* shear);
   void create_particles(int np, const double* pos, const double* tag, double diameter, double rho,
                         int type, const double* vel);

@@ -1275,14 +1275,23 @@ void DemEngine::compute_grid()
   // wrapped stencil never meets the same atom twice
   ghost_free_ = opt_ghost_free_ != 0 && !have_subdomain_ && opt_tile_ <= 1 && !opt_lds_ && roots_ &&
                 (periodic_[0] || periodic_[1] || periodic_[2]);
+  // Cells of the cutoff that fit a length.  One fewer when they fill it to within rounding: a cell as wide as the cutoff
+  // exactly lets floor((x - lo) * inv), with inv rounded, put two atoms that are one cutoff apart (both on cell corners)
+  // two cells apart, outside the stencil.  Cell coordinates stay below 2^11, so their rounding error stays below 2^-41: with
+  // the cell at least 1 + 2^-40 cutoffs wide, two atoms within the cutoff are never more than `stencil` cells apart.
+  auto cells_of = [cut](double len) {
+    int n = (int)(len / cut);
+    if (n > 1 && len <= (double)n * cut * (1.0 + 0x1p-40)) n--;
+    return n;
+  };
   for (int k = 0; k < 3 && ghost_free_; k++)
-    if (periodic_[k] && (ext_[k] || (int)((hi[k] - lo[k]) / cut) < 3)) ghost_free_ = false;
+    if (periodic_[k] && (ext_[k] || cells_of(hi[k] - lo[k]) < 3)) ghost_free_ = false;
   for (int k = 0; k < 3; k++) {
     const bool wrapk = ghost_free_ && periodic_[k];
     const bool ext = !wrapk && (periodic_[k] || ext_[k]);
     const double l = ext ? lo[k] - cut : lo[k];
     const double h = ext ? hi[k] + cut : hi[k];
-    int n = (int)((h - l) / cut);
+    int n = cells_of(h - l);
     n = std::max(1, std::min(n, 1 << 9)) * sub;   // cells of size >= cut / sub, searched +-sub cells
     grid_.lo[k] = l;
     grid_.n[k] = n;
@@ -2459,6 +2468,46 @@ long long DemEngine::get_history(long long max, int* tag_i, int* tag_j, double* 
     SF_HIP(hipMemcpy(shear, sh.p, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
   }
   return (long long)h;
+}
+
+long long DemEngine::get_neighbors(long long max, int* tag_i, int* tag_j, int* image, int* flags)
+{
+  if (have_subdomain_) fail("sf_dem_get_neighbors: single domain only (this engine holds one part of a decomposed domain)");
+  if (!nlocal_ || !have_list_) return 0;
+  if (max < 0) max = 0;
+  unsigned long long* d = nullptr;
+  SF_HIP(hipMalloc(&d, sizeof(unsigned long long)));
+  SF_HIP(hipMemsetAsync(d, 0, sizeof(unsigned long long), stream_));
+  ScratchI ti(max), tj(max), im(3 * (size_t)max), fl(max);
+  const int nall = nlocal_ + (nghost_ > 0 ? nghost_ : 0);
+  k_collect_neighbors<<<div_up(nlocal_, 256), 256, 0, stream_>>>(
+      neigh_.as<int>(), numneigh_.as<int>(), tag_.as<int>(), gsrc_.as<int>(), gshift_.as<double>(), nlocal_, nall, cap_,
+      double3{1.0 / (boxhi_[0] - boxlo_[0]), 1.0 / (boxhi_[1] - boxlo_[1]), 1.0 / (boxhi_[2] - boxlo_[2])}, d, max, ti.p,
+      tj.p, im.p, fl.p, roots_ ? 1 : 0);
+  unsigned long long h = 0;
+  SF_HIP(hipMemcpyAsync(&h, d, sizeof(h), hipMemcpyDeviceToHost, stream_));
+  sync();
+  (void)hipFree(d);
+  const long long n = std::min<long long>((long long)h, max);
+  if (n > 0) {
+    SF_HIP(hipMemcpy(tag_i, ti.p, sizeof(int) * n, hipMemcpyDeviceToHost));
+    SF_HIP(hipMemcpy(tag_j, tj.p, sizeof(int) * n, hipMemcpyDeviceToHost));
+    SF_HIP(hipMemcpy(image, im.p, sizeof(int) * 3 * n, hipMemcpyDeviceToHost));
+    SF_HIP(hipMemcpy(flags, fl.p, sizeof(int) * n, hipMemcpyDeviceToHost));
+  }
+  return (long long)h;
+}
+
+void DemEngine::get_build_positions(double* x, int* tag)
+{
+  if (have_subdomain_) fail("sf_dem_get_build_positions: single domain only");
+  if (!nlocal_) return;
+  if (!have_list_) fail("sf_dem_get_build_positions: no list was built yet");
+  ScratchD xs(3 * (size_t)nlocal_);
+  k_pack_build_positions<<<div_up(nlocal_, 256), 256, 0, stream_>>>(xhold_.as<double>(), nlocal_, cap_, xs.p);
+  sync();
+  SF_HIP(hipMemcpy(x, xs.p, sizeof(double) * 3 * nlocal_, hipMemcpyDeviceToHost));
+  SF_HIP(hipMemcpy(tag, tag_.as<int>(), sizeof(int) * nlocal_, hipMemcpyDeviceToHost));
 }
 
 void DemEngine::get_wall_shear(int w, double* shear)

@@ -185,4 +185,58 @@ __global__ __launch_bounds__(256) void k_collect_history(const int* neigh, const
   }
 }
 
+// every word of the full list as (owner tag, neighbour tag, image of the neighbour, flags), compacted with an atomic
+// cursor like k_collect_history.  Root mode: the image is the code of an owner-side word (a partner-side word holds the
+// owner's slot there and is never an image).  Index mode, and ghosts made on this GPU in either mode: the image is the
+// ghost's shift in box lengths, the neighbour its root.  nall = owned + ghost atoms: a word that points beyond them is
+// reported with tag -1 and never followed.  Reads only.
+__global__ __launch_bounds__(256) void k_collect_neighbors(const int* neigh, const int* numneigh, const int* tag,
+                                                           const int* gsrc, const double* gshift, int nlocal, int nall,
+                                                           size_t cap, double3 inv_prd, unsigned long long* cursor,
+                                                           long long max, int* ti, int* tj, int* image, int* fl,
+                                                           int roots)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nlocal) return;
+  const int nn = numneigh[i];
+  const int tagi = tag[i];
+  for (int s = 0; s < nn; s++) {
+    const int w = neigh[(size_t)s * cap + i];
+    int j = neigh_index(w, roots);
+    int ix = 0, iy = 0, iz = 0;
+    if (roots && (w & kOwnBit)) {
+      const int code = (w >> kIdxBits) & 31;
+      const int cz = code / 9, cy = (code - 9 * cz) / 3, cx = code - 9 * cz - 3 * cy;
+      ix = cx - 1; iy = cy - 1; iz = cz - 1;
+    }
+    int tagj = -1;
+    if (j >= 0 && j < nall) {
+      if (j >= nlocal && gsrc[j] >= 0) {
+        ix += (int)rint(gshift[j] * inv_prd.x);
+        iy += (int)rint(gshift[cap + j] * inv_prd.y);
+        iz += (int)rint(gshift[2 * cap + j] * inv_prd.z);
+        j = gsrc[j];
+      }
+      if (j >= 0 && j < nall) tagj = tag[j];
+    }
+    const long long k = (long long)atomicAdd(cursor, 1ull);
+    if (k < max) {
+      ti[k] = tagi;
+      tj[k] = tagj;
+      image[3 * k] = ix; image[3 * k + 1] = iy; image[3 * k + 2] = iz;
+      fl[k] = ((w & kTouchBit) ? 1 : 0) | ((w & kOwnBit) ? 2 : 0);
+    }
+  }
+}
+
+// xhold [3][cap] -> AoS
+__global__ __launch_bounds__(256) void k_pack_build_positions(const double* xhold, int n, size_t cap, double* x)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  x[3 * i] = xhold[i];
+  x[3 * i + 1] = xhold[cap + i];
+  x[3 * i + 2] = xhold[2 * cap + i];
+}
+
 }  // namespace sf

@@ -1042,6 +1042,20 @@ long long sf_dem_get_history(void* ptr, long long max, int* tag_i, int* tag_j, d
   SF_API_END(n)
 }
 
+long long sf_dem_get_neighbors(void* ptr, long long max, int* tag_i, int* tag_j, int* image, int* flags)
+{
+  SF_API_BEGIN
+  const long long n = H(ptr)->eng.get_neighbors(max, tag_i, tag_j, image, flags);
+  SF_API_END(n)
+}
+
+int sf_dem_get_build_positions(void* ptr, double* x, int* tag)
+{
+  SF_API_BEGIN
+  H(ptr)->eng.get_build_positions(x, tag);
+  SF_API_END(0)
+}
+
 int sf_dem_get_wall_shear(void* ptr, int w, double* shear)
 {
   SF_API_BEGIN

@@ -386,6 +386,24 @@ class Lammps:
         n = check(self.L.sf_dem_get_history(self.ptr, cap, _p(ti), _p(tj), _p(sh)))
         return {(int(a), int(b)): s.copy() for a, b, s in zip(ti[:n], tj[:n], sh[:n])}
 
+    def neighbors(self):
+        """every word of the full list of the owned atoms, in no particular order: an (n, 5) int array of
+        tag_i, tag_j, sx, sy, sz (which periodic image of j; 0 0 0 = j itself) and the flags (bit 0: the pair touches,
+        bit 1: this side stores the pair's history).  Single domain only; changes nothing."""
+        cap = max(int(self.info().npairs_full), 1)
+        ti = np.zeros(cap, np.int32); tj = np.zeros(cap, np.int32)
+        im = np.zeros((cap, 3), np.int32); fl = np.zeros(cap, np.int32)
+        n = check(self.L.sf_dem_get_neighbors(self.ptr, cap, _p(ti), _p(tj), _p(im), _p(fl)))
+        assert n <= cap, (n, cap)
+        return np.column_stack([ti[:n], tj[:n], im[:n]]).astype(np.int64), fl[:n].copy()
+
+    def build_positions(self):
+        """x, tag: the positions the current list was built from (what the skin/2 check measures from), engine order"""
+        n = self.get_local_n()
+        x = np.zeros((n, 3)); tag = np.zeros(n, np.int32)
+        check(self.L.sf_dem_get_build_positions(self.ptr, _p(x), _p(tag)))
+        return x, tag
+
     def wall_shear(self, w):
         n = self.get_local_n()
         sh = np.zeros((n, 3))

@@ -7,6 +7,7 @@ import pytest
 
 from sedifoam_amd import synthetic
 from tests import dem_cases as dc
+from tests import neigh_model as nm
 
 pytestmark = pytest.mark.gpu
 
@@ -138,8 +139,15 @@ def test_periodic_hertz_bed():
     lmp, orc = _run_case(bed, BASE)
     info = lmp.info()
     assert info.nghost > 0 and info.nghost == orc.nghost
-    # full list = 2 x the oracle's half list (owned-owned pairs twice, owned-ghost pairs once each side)
-    assert info.npairs_full == 2 * (orc.npairs - 0) - 0 or info.npairs_full > orc.npairs
+    # the list as it stands after the run against the brute-force pair set at the positions it was built from
+    # (tests/neigh_model.py): the full list holds every row of it, the oracle's half list every owned-owned pair once
+    # and every (owned atom, image) pair once
+    xb, tagb = lmp.build_positions()
+    rows, band = nm.neighbor_rows(xb, 0.5 * bed["diameter"][tagb - 1], bed["boxlo"], bed["boxhi"], bed["periodic"],
+                                  BASE["skin"], tag=tagb)
+    assert band == 0
+    assert info.npairs_full == len(rows)
+    assert orc.npairs == nm.half_count(rows)
 
 
 @pytest.mark.parametrize("ghost_free", ["0", "1"])
@@ -438,10 +446,13 @@ def test_list_build_with_four_lanes_per_atom_gives_the_same_bits(monkeypatch):
             st = lmp.get_state()
             st["hist"] = lmp.history()
             st["nbuilds"] = lmp.info().nbuilds
+            rows, flags = lmp.neighbors()
+            st["words"] = sorted(map(tuple, np.column_stack([rows, flags]).tolist()))
             outs.append(st)
         assert outs[0]["nbuilds"] >= 2
         for o in outs[1:]:
             assert o["nbuilds"] == outs[0]["nbuilds"]
+            assert len(o["words"]) > 0 and o["words"] == outs[0]["words"]   # the same list, word for word
             for k in ("x", "v", "omega", "f", "torque"):
                 assert np.array_equal(outs[0][k], o[k]), k
             assert set(o["hist"]) == set(outs[0]["hist"])
