@@ -201,6 +201,22 @@ int sf_lammps_global_cost(void *ptr, const char *id, double *ms);
  * on an engine filled through sf_dem_create_atoms the counts start with the first of these keywords or calls, which must
  * come before the first run.  The computes are queried through sf_lammps_compute_atom / sf_lammps_compute_global */
 int sf_lammps_get_image(void *ptr, int *out);
+/* regions and the groups made of them (`region ID style ... units box`, `group ID region RID`, `group ID dynamic PARENT
+ * region RID [every N]`, `group ID static`).  sf_lammps_region_match: out[n] = 1 where point k of xyz[3 n] matches region
+ * `id` (its side applied), evaluated on the GPU by the device function the group kernels call; the points need not lie in
+ * the box */
+int sf_lammps_region_match(void *ptr, const char *id, int n, const double *xyz, int *out);
+/* out[nlocal] = 1 for the owned atoms of group `name`, in the atom order of sf_lammps_get_local_info */
+int sf_lammps_group_mask(void *ptr, const char *name, int *out);
+/* the owned atoms of group `name`: of a dynamic group the device counter of its last evaluation, of any other group a count
+ * made now */
+long long sf_lammps_group_count(void *ptr, const char *name);
+/* launches of the region match kernels so far (one per step at which dynamic groups are due, however many are; one per
+ * `group ID region`; one per sf_lammps_region_match) */
+int sf_lammps_region_launches(void *ptr, long long *launches);
+/* measurement: GPU ms of one update of the dynamic group `name` (NULL or "": of all dynamic groups in their one launch)
+ * now, from HIP events.  Passive: it works on a copy of the mask and on counters of its own */
+int sf_lammps_region_cost(void *ptr, const char *name, double *ms);
 /* histograms (`fix ID group ave/histo Nevery Nrepeat Nfreq lo hi Nbin value ... [mode scalar|vector] [kind global|peratom|
  * local] [beyond ignore|end|extra] [ave one|running|window M] [start N] [file NAME] [overwrite] [title1|2|3 STRING]`,
  * `unfix ID`): the latest output of fix `id` -- what the last block of the fix's file holds.  *step its step, stats4 =

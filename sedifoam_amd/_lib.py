@@ -123,6 +123,11 @@ _SIGS = {
     "sf_lammps_global_launches": (C.c_int, [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "sf_lammps_global_cost": (C.c_int, [vp, C.c_char_p, dp]),
     "sf_lammps_get_image": (C.c_int, [vp, ip]),
+    "sf_lammps_region_match": (C.c_int, [vp, C.c_char_p, C.c_int, dp, ip]),
+    "sf_lammps_group_mask": (C.c_int, [vp, C.c_char_p, ip]),
+    "sf_lammps_group_count": (C.c_longlong, [vp, C.c_char_p]),
+    "sf_lammps_region_launches": (C.c_int, [vp, C.POINTER(C.c_longlong)]),
+    "sf_lammps_region_cost": (C.c_int, [vp, C.c_char_p, dp]),
     "sf_lammps_ave_histo": (C.c_longlong, [vp, C.c_char_p, C.c_longlong, C.POINTER(C.c_longlong), dp, dp, dp]),
     "sf_lammps_ave_histo_launches": (C.c_int, [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "sf_lammps_ave_histo_cost": (C.c_int, [vp, C.c_char_p, dp]),

@@ -177,7 +177,7 @@ inline std::string parse_chunk_atom(const std::vector<std::string>& w, const dou
       if (w[k + 1] != "no") return illegal;
       k += 2;
     } else if (key == "region") {
-      return "compute chunk/atom: region is not supported (there is no region command)";
+      return "compute chunk/atom: region is not supported (give the compute a region group: group ID region RID, or group ID dynamic)";
     } else
       return illegal;
   }

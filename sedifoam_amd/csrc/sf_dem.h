@@ -352,6 +352,11 @@ class DemEngine {
   int group_bit(const std::string& name) const;
   void group_type(const std::string& name, int op, int v1, int v2, const std::vector<int>& list);
   void group_combine(const std::string& name, int mode, const std::vector<std::string>& args);
+  // the bit of group `name`, made if there is no such group yet (no atom in it): group ID region / dynamic (sf_region.hip)
+  int group_make(const std::string& name) { return new_group_bit(name); }
+  // does a fix the sub-step kernel or the rigid integrator implements (nve/sphere, gravity, fdrag, freeze, a wall,
+  // rigid/nve) act on this group bit?  Whichever way the fix was set: a script line or a setter (sf_rigid.hip)
+  bool fix_uses_group_bit(int bit) const;
   void set_velocity_group(int groupbit, double vx, double vy, double vz);
   // the wall registered last: `zcylinder radius` instead of a plane pair / wiggle (kind 1: axis amplitude period) or
   // shear (kind 2: axis vshear)

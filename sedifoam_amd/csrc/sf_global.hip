@@ -719,7 +719,7 @@ bool global_compute_style(const std::string& style)
 
 void global_compute_define(SfLammps& L, const std::vector<std::string>& w)
 {
-  if (w[3] == "reduce/region") fail("compute reduce/region is not supported (there is no region command): compute reduce is");
+  if (w[3] == "reduce/region") fail("compute reduce/region is not supported: compute reduce on a region group is (group ID region RID, or group ID dynamic)");
   auto c = std::make_unique<GlobalCompute>();
   c->id = w[1];
   c->groupbit = L.eng.group_bit(w[2]);

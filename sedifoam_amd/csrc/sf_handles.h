@@ -55,8 +55,12 @@ struct SfLammps {
   // (sf_displace.hip); opaque like halo
   void* displace = nullptr;
   void (*displace_delete)(void*) = nullptr;
+  // the regions, the dynamic groups, their programs and member counts on the device (sf_region.hip); opaque like halo
+  void* regions = nullptr;
+  void (*regions_delete)(void*) = nullptr;
   ~SfLammps()
   {
+    if (regions && regions_delete) regions_delete(regions);
     if (displace && displace_delete) displace_delete(displace);
     if (restart && restart_delete) restart_delete(restart);
     if (thermo && thermo_delete) thermo_delete(thermo);   // (closes the log and screen files)

@@ -25,6 +25,7 @@
 #include "sf_histo.h"
 #include "sf_restart.h"
 #include "sf_displace.h"
+#include "sf_region.h"
 #include "sf_rigid.h"
 #include "sf_roctx.h"
 #include "sf_thermo.h"
@@ -155,22 +156,25 @@ void advance(SfLammps& L, int n)
 // reduction, then the next piece begins with its initial integrate -- what consecutive `run N pre no post no` calls do),
 // and the frame of the current step is written first if it is due ([3P] Output::setup: step 0 at the setup of the first
 // run).  A fix ave/chunk, ave/time or ave/histo cuts the run at its sample steps in the same way.  Without a dump, a thermo
-// destination, a restart schedule or such a fix the run is not cut.
+// destination, a restart schedule or such a fix the run is not cut.  A dynamic group cuts it at the multiples of its N in the
+// same way (its membership is decided there, before the outputs of that step read it); a cut is not a setup.
 void sf::run_steps(SfLammps& L, int n)
 {
+  const bool dyn = sf::region_next_step(L, L.eng.nsteps()) >= 0;   // (there is a dynamic group)
   const bool thermo = sf::thermo_active(L), rst = sf::restart_active(L);
   const bool ave = sf::ave_fix_next_step(L, L.eng.nsteps()) >= 0;   // (there is an averaging fix)
   if (thermo && L.eng.rigid_on() && sf::thermo_needs_dof(L))
     sf::fail("thermo output with temp / press / ke / etotal / p** needs the degrees of freedom of the rigid bodies, which "
              "fix rigid/nve does not keep yet: use thermo_style custom without them, or -screen none -log none");
   sf::restart_run_begin(L);   // (wall rows of a restart file that no fix claimed are dropped here; host only)
-  if (!sf::dump_active(L) && !thermo && !rst && !ave) {
+  if (!sf::dump_active(L) && !thermo && !rst && !ave && !dyn) {
     L.eng.set_thermo_virial(false);
     advance(L, n);
     return;
   }
   if (thermo) sf::thermo_run_begin(L);   // (the first run: the virial of the setup evaluation)
   advance(L, 0);   // (setup: the frame of the first step holds the forces of the setup evaluation)
+  if (dyn) sf::region_begin_due(L);   // (the setup of a `run`; a group not evaluated since its definition)
   sf::dump_write_due(L);
   // the samples of the averaging fixes whose step is this one (they sample at the setup of a run too), and in the same plan
   // of global computes the c_ columns of the thermo line
@@ -186,7 +190,9 @@ void sf::run_steps(SfLammps& L, int n)
     }
     if (rst) next = std::min(next, sf::restart_next_step(L, L.eng.nsteps()));
     if (ave) next = std::min(next, sf::ave_fix_next_step(L, L.eng.nsteps()));
+    if (dyn) next = std::min(next, sf::region_next_step(L, L.eng.nsteps()));
     advance(L, (int)(next - L.eng.nsteps()));
+    if (dyn) sf::region_step_due(L);
     sf::dump_write_due(L);
     sf::ave_fix_step_due(L, sf::thermo_global_ids_due(L, false, 0));
     if (rst) sf::restart_write_due(L);
@@ -296,6 +302,8 @@ void read_data(SfLammps& L, const std::string& path, bool molecules = false)
 void read_restart(SfLammps& L, const std::string& path)
 {
   if (L.eng.box_defined() || L.decomposed) sf::fail("Cannot read_restart after simulation box is defined");
+  if (sf::region_dynamic_any(L))   // (the file's groups replace the engine's: a dynamic group's bits would be stale)
+    sf::fail("Cannot read_restart while a dynamic group is defined (group ID static first, and define it again afterwards)");
   sf::RestartData d;
   sf::restart_file_read(path, d);
   L.eng.set_periodic(d.periodic[0], d.periodic[1], d.periodic[2]);
@@ -375,6 +383,7 @@ void cmd_fix(SfLammps& L, const std::vector<std::string>& w)
   const int gb = L.eng.group_bit(w[2]);   // "Could not find fix group ID" in LAMMPS
   const std::string& st = w[3];
   const int narg = (int)w.size() - 1;  // LAMMPS narg counts ID group style ...
+  sf::region_refuse_engine_fix(L, st, w[2]);   // (a dynamic group is for the readers: computes, dumps, averaging fixes)
   // LAMMPS runs the post_force fixes in script order.  The fused kernel adds gravity, fdrag and the walls in that
   // fixed order (sums only: order-free up to rounding); what matters is on which side of `fix freeze` a fix stands --
   // the reference's bed cases put `fix ywall all wall/gran` AFTER `fix 4 bottom freeze`, so the wall still pushes
@@ -468,7 +477,10 @@ void cmd_fix(SfLammps& L, const std::vector<std::string>& w)
       if (w.size() < 6) sf::fail("Illegal fix rigid/nve command");
       const int ng = inum(w[5]);
       if (ng < 1 || w.size() < 6 + (size_t)ng) sf::fail("Illegal fix rigid/nve command");
-      for (int k = 0; k < ng; k++) gbits.push_back(L.eng.group_bit(w[6 + k]));
+      for (int k = 0; k < ng; k++) {
+        sf::region_refuse_engine_fix(L, st, w[6 + k]);
+        gbits.push_back(L.eng.group_bit(w[6 + k]));
+      }
       iarg = 6 + (size_t)ng;
       bodystyle = 1;
     } else
@@ -481,13 +493,25 @@ void cmd_fix(SfLammps& L, const std::vector<std::string>& w)
     sf::fail("Unknown fix style %s", st.c_str());
 }
 
-// [3P] group ID style args: the styles the reference's input scripts use (type, subtract, union, intersect)
+// [3P] group ID style args: the styles the reference's input scripts use (type, subtract, union, intersect), and region,
+// dynamic and static (sf_region.hip)
 void cmd_group(SfLammps& L, const std::vector<std::string>& w)
 {
+  if (w.size() == 3 && w[2] == "static") {
+    sf::group_static_command(L, w);
+    return;
+  }
   if (w.size() < 4) sf::fail("Illegal group command");
   const std::string& name = w[1];
   const std::string& style = w[2];
-  if (style == "type") {
+  if (style != "dynamic" && sf::group_is_dynamic(L, name))
+    sf::fail("group %s %s: %s is a dynamic group, only its region decides its atoms (group %s static first)", name.c_str(),
+             style.c_str(), name.c_str(), name.c_str());
+  if (style == "region") {
+    sf::group_region_command(L, w);
+  } else if (style == "dynamic") {
+    sf::group_dynamic_command(L, w);
+  } else if (style == "type") {
     static const char* ops[] = {"<", "<=", ">", ">=", "==", "!=", "<>"};
     int op = 0;
     for (int k = 0; k < 7; k++)
@@ -504,7 +528,8 @@ void cmd_group(SfLammps& L, const std::vector<std::string>& w)
     std::vector<std::string> args(w.begin() + 3, w.end());
     L.eng.group_combine(name, style == "subtract" ? 0 : (style == "union" ? 1 : 2), args);
   } else
-    sf::fail("group style %s is not supported by this engine (type, subtract, union, intersect are)", style.c_str());
+    sf::fail("group style %s is not supported by this engine (type, subtract, union, intersect, region, dynamic, static are)",
+             style.c_str());
 }
 
 void command(SfLammps& L, const std::string& line)
@@ -568,6 +593,8 @@ void command(SfLammps& L, const std::string& line)
       L.eng.set_velocity_group(L.eng.group_bit(w[1]), num(w[3]), num(w[4]), num(w[5]));
     } else
       sf::fail("velocity: only `velocity GROUP set vx vy vz` is supported");
+  } else if (c == "region") {
+    sf::region_command(L, w);
   } else if (c == "group") {
     cmd_group(L, w);
   } else if (c == "fix" && w.size() > 3 && w[3] == "ave/time") {
@@ -582,6 +609,7 @@ void command(SfLammps& L, const std::string& line)
     sf::unfix_command(L, w);
   } else if (c == "run") {
     if (w.size() < 2) sf::fail("Illegal run command");
+    sf::region_run_setup(L);   // ([3P] FixGroup::setup: a run's setup evaluates every dynamic group)
     run_steps(L, inum(w[1]));
     sf::dump_drain(L);   // (a script's run returns with its frames in their files)
     sf::restart_drain(L);   // (... and its checkpoints)

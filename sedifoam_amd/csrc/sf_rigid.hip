@@ -501,6 +501,21 @@ void DemEngine::rigid_define(int bodystyle, int groupbit, const std::vector<int>
   use_groups_ = use_groups_ || groupbit != 1 || bodystyle == 1;
 }
 
+bool DemEngine::fix_uses_group_bit(int bit) const
+{
+  if ((have_nve_ && nve_bit_ == bit) || (have_gravity_ && grav_bit_ == bit) || (have_fdrag_ && fdrag_bit_ == bit) ||
+      (freeze_bit_ && freeze_bit_ == bit))
+    return true;
+  for (int k = 0; k < nwalls_; k++)
+    if (walls_[k].bit == bit) return true;
+  if (rigid_) {
+    if (rigid_->groupbit == bit) return true;
+    for (int b : rigid_->groupbits)
+      if (b == bit) return true;
+  }
+  return false;
+}
+
 void DemEngine::rigid_dirty()
 {
   if (rigid_) rigid_->dirty = true;

@@ -271,6 +271,37 @@ class Lammps:
         check(self.L.sf_lammps_get_image(self.ptr, _p(out)))
         return out
 
+    def region_match(self, rid, points):
+        """bool per point of `points` (n, 3): does it match region `rid` (its side applied)?  Evaluated on the GPU by the
+        device function the group kernels call; the points need not lie in the box"""
+        p = _f64(points).reshape(-1, 3)
+        out = np.zeros(p.shape[0], np.int32)
+        check(self.L.sf_lammps_region_match(self.ptr, str(rid).encode(), p.shape[0], _p(p), _p(out)))
+        return out.astype(bool)
+
+    def group_mask(self, name):
+        """bool per owned atom, in the atom order of get_local_info(): is it in group `name`?"""
+        out = np.zeros(self.get_local_n(), np.int32)
+        check(self.L.sf_lammps_group_mask(self.ptr, str(name).encode(), _p(out)))
+        return out.astype(bool)
+
+    def group_count(self, name):
+        """the owned atoms of group `name`: of a dynamic group the device counter of the last launch that evaluated or counted
+        it; of any other group, and of a dynamic group no launch has counted since its definition, a count made now"""
+        return check(self.L.sf_lammps_group_count(self.ptr, str(name).encode()))
+
+    def region_launches(self):
+        """launches of the region match kernels so far (one per step at which dynamic groups are due, however many)"""
+        n = C.c_longlong()
+        check(self.L.sf_lammps_region_launches(self.ptr, C.byref(n)))
+        return n.value
+
+    def region_cost(self, name=None):
+        """GPU ms of one update of the dynamic group `name` (None: of all dynamic groups in their one launch) now; passive"""
+        ms = C.c_double()
+        check(self.L.sf_lammps_region_cost(self.ptr, str(name).encode() if name else None, C.byref(ms)))
+        return ms.value
+
     def ave_histo(self, fid):
         """the latest output of `fix fid group ave/histo ...`: dict(step, nbins, total, missing, min, max, coord[nbins],
         count[nbins], frac[nbins] (count / total, 0 when total is 0)) -- what the last block of the fix's file holds.  An
