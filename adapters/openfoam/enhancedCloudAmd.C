@@ -263,21 +263,10 @@ void enhancedCloud::readProperties
     }
     pr.smoothDirection[0] = sd.xx(); pr.smoothDirection[1] = sd.yy(); pr.smoothDirection[2] = sd.zz();
 
-    // the add / delete schedules are not part of the library; the inlet override of updateDragOnParticles is
+    // the inlet override of updateDragOnParticles; the add / delete schedules the same variable switches on: readFeed
     pr.addParticleOption = cloudProperties_.lookupOrDefault<label>("addParticle", 0);
-    if
-    (
-        cloudProperties_.lookupOrDefault<label>("deleteParticle", 0) > 0
-     || cloudProperties_.lookupOrDefault<label>("deleteBeforeAdd", 0) > 0
-    )
-    {
-        FatalErrorIn("enhancedCloud::readProperties")
-            << "deleteParticle / deleteBeforeAdd: particle delete schedules are not supported" << abort(FatalError);
-    }
     if (pr.addParticleOption > 0)
     {
-        Info<< "*** addParticle " << pr.addParticleOption
-            << ": the inlet force override is applied, NO particles are added (schedule not supported)" << endl;
         const vector f = cloudProperties_.lookupOrDefault<vector>("inletForce", vector::zero);
         const vector e = cloudProperties_.lookupOrDefault<vector>("eccentricity", vector::zero);
         const tensor b = cloudProperties_.lookupOrDefault<tensor>("inletBox", tensor::zero);
@@ -288,6 +277,55 @@ void enhancedCloud::readProperties
             pr.inletBox[k] = b.component(k);
         }
     }
+}
+
+
+// the add / delete schedules of constant/cloudProperties -> sf_cloud_feed; keys and defaults of
+// softParticleCloud.C:450-513.  false: neither addParticle nor deleteParticle is set, nothing to configure
+bool enhancedCloud::readFeed(sf_cloud_feed& fd)
+{
+    std::memset(&fd, 0, sizeof(fd));
+    fd.addParticle = cloudProperties_.lookupOrDefault<label>("addParticle", 0);
+    fd.deleteParticle = cloudProperties_.lookupOrDefault<label>("deleteParticle", 0);
+    fd.deleteBeforeAdd = cloudProperties_.lookupOrDefault<label>("deleteBeforeAdd", 0);
+    if (fd.addParticle <= 0 && fd.deleteParticle <= 0)
+    {
+        return false;
+    }
+    const vector e = cloudProperties_.lookupOrDefault<vector>("eccentricity", vector::zero);
+    fd.eccentricity[0] = e.x(); fd.eccentricity[1] = e.y(); fd.eccentricity[2] = e.z();
+    tensor add(tensor::zero), del(tensor::zero), clr(tensor::zero);
+    if (fd.addParticle > 0)
+    {
+        fd.addParticleTimeStep = readScalar(cloudProperties_.lookup("addParticleTimeStep"));
+        fd.randomPerturb = readScalar(cloudProperties_.lookup("randomPerturb"));
+        add = cloudProperties_.lookupOrDefault<tensor>("addParticleBox", tensor::zero);
+        if (!cloudProperties_.found("addParticleInfo"))
+        {
+            FatalErrorIn("enhancedCloud::readFeed")
+                << "keyword addParticleInfo is undefined in dictionary cloudProperties" << abort(FatalError);
+        }
+        const vector info = cloudProperties_.lookupOrDefault<vector>("addParticleInfo", vector::zero);
+        const vector v = cloudProperties_.lookupOrDefault<vector>("addParticleVelocity", vector::zero);
+        fd.addParticleInfo[0] = info.x(); fd.addParticleInfo[1] = info.y(); fd.addParticleInfo[2] = info.z();
+        fd.addParticleVelocity[0] = v.x(); fd.addParticleVelocity[1] = v.y(); fd.addParticleVelocity[2] = v.z();
+        fd.reduceNumberFactor = cloudProperties_.lookupOrDefault<label>("reduceNumberFactor", 1);
+    }
+    if (fd.deleteParticle > 0)
+    {
+        del = cloudProperties_.lookupOrDefault<tensor>("deleteParticleBox", tensor::zero);
+    }
+    if (fd.deleteBeforeAdd > 0)
+    {
+        clr = cloudProperties_.lookupOrDefault<tensor>("clearInitialBox", tensor::zero);
+    }
+    for (direction k = 0; k < 9; k++)
+    {
+        fd.addParticleBox[k] = add.component(k);
+        fd.deleteParticleBox[k] = del.component(k);
+        fd.clearInitialBox[k] = clr.component(k);
+    }
+    return true;
 }
 
 
@@ -462,6 +500,19 @@ enhancedCloud::enhancedCloud
         sf_cloud_create(sedifoam_shim::h(lmp_), &m, &pr, runTime_.deltaTValue(), &cloud_),
         "enhancedCloud::enhancedCloud"
     );
+    sf_cloud_feed fd;
+    if (readFeed(fd))
+    {
+        if (Pstream::parRun())
+        {
+            FatalErrorIn("enhancedCloud::enhancedCloud")
+                << "addParticle / deleteParticle: the add / delete schedules run on one rank" << abort(FatalError);
+        }
+        sfCheck(sf_cloud_set_feed(cloud_, &fd), "enhancedCloud::enhancedCloud");
+        Info<< "*** addParticle " << fd.addParticle << " deleteParticle " << fd.deleteParticle
+            << " deleteBeforeAdd " << fd.deleteBeforeAdd << ": " << sf_cloud_feed_cells(cloud_, NULL, 0)
+            << " add cells" << endl;
+    }
     int sc = 1, ss = 1, nc = 0;
     sfCheck(sf_cloud_sub_cycling(cloud_, &sc, &ss), "enhancedCloud::enhancedCloud");
     subCycles_ = sc;
@@ -506,6 +557,7 @@ void enhancedCloud::evolve()
     if (!Pstream::parRun())
     {
         sfCheck(sf_cloud_evolve(cloud_), "enhancedCloud::evolve");
+        particleCount_ = lammps_get_global_n(lmp_);   // (the add / delete schedules run inside, enhancedCloud.C:713-718)
     }
     else
     {

@@ -565,8 +565,8 @@ typedef struct {
    * softParticleCloud.C:460-486): with addParticleOption 1 (box) or 2 (hollow cylinder) and a non-zero inletForce, a
    * particle inside inletBox gets pDrag = m (inletForce - U) / deltaT instead of the assembled force.  inletBox holds
    * the tensor's nine components x1 x2 y1 y2 z1 z2 r1 r2 (unused) as pointInRegion reads them
-   * (softParticleCloud.C:1354-1417); eccentricity shifts the inner cylinder.  The add / delete schedules that
-   * addParticleOption also switches on in the reference are not part of this library. */
+   * (softParticleCloud.C:1354-1417); eccentricity shifts the inner cylinder.  The add / delete schedules that the same
+   * variable switches on in the reference are configured through sf_cloud_set_feed below. */
   int addParticleOption;
   double inletForce[3];
   double inletBox[9];
@@ -658,6 +658,44 @@ typedef struct {
   double evolve, calcTc, dragOnParticles, lammps, particleMove, scatter;
 } sf_cloud_timers;
 int sf_cloud_get_timers(void *cloud, sf_cloud_timers *t);
+
+/* The cloud's particle add / delete schedules (cloudProperties keys read at softParticleCloud.C:450-513; the routines
+ * :1099-1352 and enhancedCloud.C:694-711, 1015-1294), decided on the GPU.  One rank, single domain.  Call after
+ * sf_cloud_create and before the first sf_cloud_evolve.  Per sub-cycle, before the drag assembly:
+ *   addParticle > 0 and timeToAddParticle <= 0: [deleteBeforeAdd and deleteParticle > 0: every type-1 grain inside
+ *     clearInitialBox goes;] one grain per add cell appears at the cell centre + randomPerturb (0.5 - u) per coordinate,
+ *     with the tags maxTag + 1 + i (maxTag: the largest tag present after the clearing); the timer restarts at
+ *     addParticleTimeStep.  Otherwise timeToAddParticle -= deltaT.
+ *   deleteParticle > 0: every type-1 grain inside deleteParticleBox goes.
+ * addParticle is the region kind of all three boxes (1 box, 2 hollow cylinder; pointInRegion, :1354-1417, is false for
+ * kind 0: deleteParticle with addParticle 0 removes nothing).  u is draw 3 i + c of drand48 after srand48(particle
+ * count): the library's own statement, not OpenFOAM's Random.  The add cells are chosen here,
+ * by findAddParticleCells (:1271-1352) on the cell centres in label order. */
+typedef struct {
+  int addParticle;            /* 0, 1 or 2; where this and sf_cloud_props.addParticleOption are both non-zero they must agree
+                               * (a struct cannot leave a field out: 0 is "not given"); with addParticleOption 0 the inlet
+                               * override takes this value, the reference having one variable for both */
+  int deleteParticle, deleteBeforeAdd;
+  double addParticleTimeStep, randomPerturb;
+  double addParticleBox[9], deleteParticleBox[9], clearInitialBox[9];
+  double eccentricity[3];
+  double addParticleInfo[3];  /* diameter, density, type */
+  double addParticleVelocity[3];
+  int reduceNumberFactor;
+} sf_cloud_feed;
+int sf_cloud_set_feed(void *cloud, const sf_cloud_feed *feed);
+/* sf_cloud_evolve runs the schedules itself, in front of the drag assembly of every sub-cycle.  A caller that drives a
+ * single rank through sf_cloud_phase runs them with phase 7, in front of phase 1; with the schedules set, phase 1 without
+ * it is refused, so that they cannot be left out unnoticed. */
+typedef struct {
+  long long totalAdd, totalDelete, totalDeleteBeforeAdd;   /* the reference's running totals */
+  double timeToAddParticle;
+  int nAddCells;
+  int lastAdd, lastDelete, lastDeleteBeforeAdd;            /* of the last sub-cycle */
+} sf_cloud_feed_stats;
+int sf_cloud_feed_info(void *cloud, sf_cloud_feed_stats *stats);
+/* the add cells' labels in the reference's order into cells[0 .. cap); returns their number (cells may be NULL) */
+int sf_cloud_feed_cells(void *cloud, int *cells, int cap);
 
 #ifdef __cplusplus
 }

@@ -75,6 +75,22 @@ class CloudMesh(C.Structure):
                 ("periodic", C.c_int * 3), ("slab_nx_global", C.c_int)]
 
 
+class CloudFeed(C.Structure):
+    """sf_cloud_feed: the add / delete schedules of cloudProperties"""
+    _fields_ = [("addParticle", C.c_int), ("deleteParticle", C.c_int), ("deleteBeforeAdd", C.c_int),
+                ("addParticleTimeStep", C.c_double), ("randomPerturb", C.c_double),
+                ("addParticleBox", C.c_double * 9), ("deleteParticleBox", C.c_double * 9),
+                ("clearInitialBox", C.c_double * 9), ("eccentricity", C.c_double * 3),
+                ("addParticleInfo", C.c_double * 3), ("addParticleVelocity", C.c_double * 3),
+                ("reduceNumberFactor", C.c_int)]
+
+
+class CloudFeedStats(C.Structure):
+    _fields_ = [("totalAdd", C.c_longlong), ("totalDelete", C.c_longlong), ("totalDeleteBeforeAdd", C.c_longlong),
+                ("timeToAddParticle", C.c_double), ("nAddCells", C.c_int), ("lastAdd", C.c_int),
+                ("lastDelete", C.c_int), ("lastDeleteBeforeAdd", C.c_int)]
+
+
 class CloudTimers(C.Structure):
     _fields_ = [("evolve", C.c_double), ("calcTc", C.c_double), ("dragOnParticles", C.c_double),
                 ("lammps", C.c_double), ("particleMove", C.c_double), ("scatter", C.c_double)]
@@ -246,6 +262,9 @@ _SIGS = {
     "sf_cloud_average_info": (C.c_int, [vp, dp]),
     "sf_cloud_adjust_timestep": (C.c_int, [C.c_double, C.c_double, C.c_int, dp, ip, ip, ip]),
     "sf_cloud_get_timers": (C.c_int, [vp, C.POINTER(CloudTimers)]),
+    "sf_cloud_set_feed": (C.c_int, [vp, C.POINTER(CloudFeed)]),
+    "sf_cloud_feed_info": (C.c_int, [vp, C.POINTER(CloudFeedStats)]),
+    "sf_cloud_feed_cells": (C.c_int, [vp, ip, C.c_int]),
 }
 
 _lib = None

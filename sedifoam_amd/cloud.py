@@ -62,8 +62,13 @@ class enhancedCloud:
 
     cloudDict keys (constant/cloudProperties): dragModel, subCycles, particleDrag, particlePressureGrad,
     particleBuoyancy, particleAddedMass, particleLift, particleHistoryForce, lubricationForce, addParticleOption +
-    inletForce + inletBox + eccentricity (the inlet override only), g, maxPossibleAlpha, diffusionBandWidth,
-    diffusionSteps, UfSmooth, UpSmooth, dragSmooth, alphaSmooth, smoothDirection.
+    inletForce + inletBox + eccentricity (the inlet override), g, maxPossibleAlpha, diffusionBandWidth,
+    diffusionSteps, UfSmooth, UpSmooth, dragSmooth, alphaSmooth, smoothDirection;
+    the add / delete schedules (one rank; softParticleCloud.C:450-513): addParticle (0 | 1 box | 2 hollow cylinder, the
+    region kind of all three boxes), deleteParticle, deleteBeforeAdd, addParticleTimeStep, randomPerturb, addParticleBox,
+    eccentricity, addParticleInfo (diameter density type), addParticleVelocity, reduceNumberFactor, deleteParticleBox,
+    clearInitialBox.  addParticle without addParticleOption also selects the inlet override (the reference has one
+    variable); both given and different is refused.
     transDict keys (constant/transportProperties): rhob, nub."""
 
     def __init__(self, lammps, mesh_origin, mesh_dx, mesh_n, cloudDict, transDict, deltaT, driver=None,
@@ -100,8 +105,16 @@ class enhancedCloud:
         pr.lubricationForce = int(cloudDict.get("lubricationForce", False))           # :597
         pr.particleHistoryForce = int(cloudDict.get("particleHistoryForce", False))   # :595-596
         # the inlet override of updateDragOnParticles (:249-257): addParticleOption 1 | 2, inletForce, inletBox (the
-        # tensor's nine numbers), eccentricity -- softParticleCloud.C:460-486; the add / delete schedules are not built
-        pr.addParticleOption = int(cloudDict.get("addParticleOption", 0))
+        # tensor's nine numbers), eccentricity -- softParticleCloud.C:460-486; the add / delete schedules: _feed_keys
+        feed = self._feed_keys(cloudDict)
+        if feed is not None and driver is not None:
+            raise SfError("enhancedCloud: the add / delete schedules (addParticle, deleteParticle) run on one rank, "
+                          "not with a driver")
+        if "addParticle" in cloudDict and "addParticleOption" in cloudDict and \
+                int(cloudDict["addParticle"]) != int(cloudDict["addParticleOption"]):
+            raise SfError("enhancedCloud: addParticle %d and addParticleOption %d differ (the reference has one variable)"
+                          % (int(cloudDict["addParticle"]), int(cloudDict["addParticleOption"])))
+        pr.addParticleOption = int(cloudDict.get("addParticleOption", cloudDict.get("addParticle", 0)))
         pr.inletForce = (C.c_double * 3)(*cloudDict.get("inletForce", (0.0, 0.0, 0.0)))
         pr.inletBox = (C.c_double * 9)(*cloudDict.get("inletBox", (0.0,) * 9))
         pr.eccentricity = (C.c_double * 3)(*cloudDict.get("eccentricity", (0.0, 0.0, 0.0)))
@@ -171,6 +184,12 @@ class enhancedCloud:
             driver.setup()
         check(self.L.sf_cloud_create(lammps.ptr, C.byref(m), C.byref(pr), float(deltaT), C.byref(h)))
         self.ptr = h
+        if feed is not None:
+            try:
+                check(self.L.sf_cloud_set_feed(self.ptr, C.byref(feed)))
+            except SfError:
+                self.close()
+                raise
         if driver is not None:
             sc = C.c_int(); ss = C.c_int()
             check(self.L.sf_cloud_sub_cycling(self.ptr, C.byref(sc), C.byref(ss)))
@@ -187,6 +206,51 @@ class enhancedCloud:
             else:
                 # the constructor scattered this rank's particles only: redo it over all ranks
                 self._phase(2); self._sum_over_ranks("gamma", "Ue"); self._phase(3); self._phase(6)
+
+    @staticmethod
+    def _feed_keys(cloudDict):
+        """the sf_cloud_feed of a cloudDict, None when it holds neither addParticle nor deleteParticle (then nothing of the
+        schedules is configured).  Keys and defaults as softParticleCloud.C:450-513 reads them: with addParticle > 0,
+        addParticleTimeStep, randomPerturb and addParticleInfo are required."""
+        if "addParticle" not in cloudDict and "deleteParticle" not in cloudDict:
+            return None
+        f = _lib.CloudFeed()
+        f.addParticle = int(cloudDict.get("addParticle", 0))
+        f.deleteParticle = int(cloudDict.get("deleteParticle", 0))
+        f.deleteBeforeAdd = int(cloudDict.get("deleteBeforeAdd", 0))
+        zero9 = (0.0,) * 9
+        if f.addParticle > 0:
+            for k in ("addParticleTimeStep", "randomPerturb", "addParticleInfo"):
+                if k not in cloudDict:
+                    raise SfError("enhancedCloud: keyword %s is undefined in cloudProperties (addParticle %d)"
+                                  % (k, f.addParticle))
+            f.addParticleTimeStep = float(cloudDict["addParticleTimeStep"])
+            f.randomPerturb = float(cloudDict["randomPerturb"])
+            f.addParticleBox = (C.c_double * 9)(*cloudDict.get("addParticleBox", zero9))
+            f.addParticleInfo = (C.c_double * 3)(*cloudDict["addParticleInfo"])
+            f.addParticleVelocity = (C.c_double * 3)(*cloudDict.get("addParticleVelocity", (0.0, 0.0, 0.0)))
+            f.reduceNumberFactor = int(cloudDict.get("reduceNumberFactor", 1))
+        f.eccentricity = (C.c_double * 3)(*cloudDict.get("eccentricity", (0.0, 0.0, 0.0)))
+        if f.deleteParticle > 0:
+            f.deleteParticleBox = (C.c_double * 9)(*cloudDict.get("deleteParticleBox", zero9))
+        if f.deleteBeforeAdd > 0:
+            f.clearInitialBox = (C.c_double * 9)(*cloudDict.get("clearInitialBox", zero9))
+        return f
+
+    def feedInfo(self):
+        """the add / delete schedules so far: dict(totalAdd, totalDelete, totalDeleteBeforeAdd, timeToAddParticle,
+        nAddCells, lastAdd, lastDelete, lastDeleteBeforeAdd -- the three counts of the last sub-cycle)"""
+        st = _lib.CloudFeedStats()
+        check(self.L.sf_cloud_feed_info(self.ptr, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def addParticleCells(self):
+        """labels of the cells a grain is added to (findAddParticleCells, softParticleCloud.C:1271-1352), in its order"""
+        n = check(self.L.sf_cloud_feed_cells(self.ptr, None, 0))
+        cells = np.zeros(n, np.int32)
+        if n:
+            check(self.L.sf_cloud_feed_cells(self.ptr, _p(cells), n))
+        return cells
 
     def close(self):
         if getattr(self, "ptr", None):

@@ -12,19 +12,19 @@
 // assemble/transpose/flatten/tag-sort marshalling (softParticleCloud.C:716-846, 970-1089) has no
 // counterpart here.
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <vector>
 
 #include "../../include/sedifoam_amd.h"
 #include "sf_dump.h"
 #include "sf_env.h"
+#include "sf_feed.h"
 #include "sf_handles.h"
 #include "sf_roctx.h"
 #include "sf_smooth.h"
 
 namespace sf {
-
-constexpr double kRootVSmall = 1.0e-150;  // OpenFOAM ROOTVSMALL (double precision)
 
 __device__ __forceinline__ double jd_ergun_wenyu(double Ur, double alpha, double pd, double nuf, double rhof)
 {
@@ -138,28 +138,6 @@ struct CloudFlagsDev {
   int inletOption;   // 0: no inlet override ; 1 box ; 2 hollow cylinder (addParticleOption with a non-zero inletForce)
   double inletForce[3], inletBox[9], ecc[3];
 };
-
-// softParticleCloud::pointInRegion  softParticleCloud.C:1354-1417 (option 1: box, faces included; option 2: between the
-// cylinders r1 -- shifted by the eccentricity -- and r2 around the axis (x1,y1,z1)-(x2,y2,z2); as there, the inner
-// distance uses the projection of the UNshifted point)
-__device__ __forceinline__ bool point_in_region(int option, const double* b, const double* ecc, double px, double py,
-                                                double pz)
-{
-  const double x1 = b[0], x2 = b[1], y1 = b[2], y2 = b[3], z1 = b[4], z2 = b[5], r1 = b[6], r2 = b[7];
-  if (option == 1)
-    return (px - x1) * (px - x2) < kRootVSmall && (py - y1) * (py - y2) < kRootVSmall && (pz - z1) * (pz - z2) < kRootVSmall;
-  if (option == 2) {
-    const double a[3] = {x2 - x1, y2 - y1, z2 - z1}, q[3] = {px - x1, py - y1, pz - z1};
-    const double h = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
-    const double dot = a[0] * q[0] + a[1] * q[1] + a[2] * q[2];
-    if (dot < 0.0 || dot > pow(h, 2)) return false;
-    const double qe[3] = {q[0] - ecc[0], q[1] - ecc[1], q[2] - ecc[2]};
-    const double dsq = (q[0] * q[0] + q[1] * q[1] + q[2] * q[2]) - dot * dot / pow(h, 2);
-    const double dsqE = (qe[0] * qe[0] + qe[1] * qe[1] + qe[2] * qe[2]) - dot * dot / pow(h, 2);
-    return dsqE > r1 * r1 && dsq < r2 * r2;
-  }
-  return false;
-}
 
 // updateParticleUr + updateParticleAlpha + Jd + updateDragOnParticles, one owned atom per lane.
 // pDrag goes straight into fix fdrag's [3][cap] array (what lammps_put_local_info would copy).
@@ -596,6 +574,7 @@ class Cloud {
           width[k][i] = mesh.faces[k][i + 1] - mesh.faces[k][i];
           if (!(width[k][i] > 0.0)) fail("cloud mesh: face coordinates along axis %d are not ascending", k);
         }
+        faces_host_[k].assign(mesh.faces[k], mesh.faces[k] + mesh.n[k] + 1);
         SF_HIP(hipMalloc(&faces_dev_[k], sizeof(double) * (mesh.n[k] + 1)));
         SF_HIP(hipMemcpy(faces_dev_[k], mesh.faces[k], sizeof(double) * (mesh.n[k] + 1), hipMemcpyHostToDevice));
         mesh_.f[k] = faces_dev_[k];
@@ -665,7 +644,7 @@ class Cloud {
     for (double* p : {V_, gamma_, Ue_, Asrc_, Omega_, Uf_, DDtUf_, gradp_, curlU_, Jd_, pDragT_, UfS_, UfSold_})
       if (p) (void)hipFree(p);
     for (void* p : {(void*)cstart_, (void*)cell_, (void*)keys_, (void*)keys2_, (void*)idx_, (void*)idx2_, sort_tmp_,
-                    (void*)faces_dev_[0], (void*)faces_dev_[1], (void*)faces_dev_[2]})
+                    (void*)faces_dev_[0], (void*)faces_dev_[1], (void*)faces_dev_[2], (void*)feed_centres_})
       if (p) (void)hipFree(p);
   }
 
@@ -718,6 +697,7 @@ class Cloud {
     advance_time();
     update_uf_smoothed();   // :675-690
     for (int k = 0; k < subCycles_; k++) {
+      feed_step();   // enhancedCloud.C:697-711: particles come and go before the drag of the sub-cycle is assembled
       double t1 = now();
       {
         Range r("foam->lammps");   // updateDragOnParticles + what lammps_put_local_info would copy
@@ -828,11 +808,21 @@ class Cloud {
         paused = update_uf_smoothed(resume);
         break;
       case 6: paused = update_uf_smoothed(resume); break;   // (re-)initialisation, no time advance
-      case 1: drag_on_particles(); break;
+      case 1:
+        // (a caller that steps through the phases must not leave the schedules out without noticing)
+        if (feed_on_ && !feed_phase_done_)
+          fail("sf_cloud_phase 1: the add / delete schedules are set; phase 7 runs them, in front of phase 1");
+        feed_phase_done_ = false;
+        drag_on_particles();
+        break;
       case 2: scatter_local(); break;
       case 3: paused = scatter_finish(resume); break;
       case 4: calc_tc_local(); break;
       case 5: paused = calc_tc_finish(resume); break;
+      case 7:   // (one rank: set_feed refuses every other arrangement)
+        feed_step();
+        feed_phase_done_ = true;
+        break;
       default: fail("sf_cloud_phase: unknown phase %d", ph);
     }
     if (paused) pending_ = ph;
@@ -904,6 +894,165 @@ class Cloud {
         for (int k = 0; k < 3; k++) pDrag[3 * r + k] = hf[(size_t)k * maxtag_ + t];
     }
   }
+
+  // ---- the add / delete schedules (sf_feed.h) ----
+  // centre of every cell, [3 ncells] in OpenFOAM label order (mesh_.C() of the reference)
+  std::vector<double> cell_centres() const
+  {
+    std::vector<double> c(3 * (size_t)mesh_.ncells);
+    for (int iz = 0; iz < mesh_.n[2]; iz++)
+      for (int iy = 0; iy < mesh_.n[1]; iy++)
+        for (int ix = 0; ix < mesh_.n[0]; ix++) {
+          const int g = ix + mesh_.n[0] * (iy + mesh_.n[1] * iz), i3[3] = {ix, iy, iz};
+          const size_t l = label_.empty() ? g : label_[g];
+          for (int k = 0; k < 3; k++) {
+            const std::vector<double>& f = faces_host_[k];
+            c[3 * l + k] = f.empty() ? mesh_.origin[k] + (i3[k] + 0.5) * mesh_.dx[k] : 0.5 * (f[i3[k]] + f[i3[k] + 1]);
+          }
+        }
+    return c;
+  }
+
+  void set_feed(const sf_cloud_feed& f)
+  {
+    DemEngine& e = lmp_->eng;
+    const char* who = "sf_cloud_set_feed";
+    if (smoother_.slab() || lmp_->world_size > 1 || lmp_->decomposed || e.nranks() > 1 || e.decomposed())
+      fail("%s: the add / delete schedules run on one rank (no driver, no slab mesh, no decomposed engine)", who);
+    if (time_index_ > 0) fail("%s: after the first evolve()", who);
+    if (e.rigid_on()) fail("%s: not while fix rigid/nve exists (its bodies are fixed sets of atoms)", who);
+    if (f.addParticle < 0 || f.addParticle > 2) fail("%s: addParticle %d is not 0, 1 or 2", who, f.addParticle);
+    if (f.addParticle && props_.addParticleOption && f.addParticle != props_.addParticleOption)
+      fail("%s: addParticle %d and addParticleOption %d differ (the reference has one variable)", who, f.addParticle,
+           props_.addParticleOption);
+    if (f.addParticle > 0 && f.reduceNumberFactor < 1)
+      fail("%s: reduceNumberFactor %d < 1 (findAddParticleCells divides by it)", who, f.reduceNumberFactor);
+    std::vector<int> cells;
+    std::vector<double> cc;
+    if (f.addParticle > 0) {
+      const std::vector<double> all = cell_centres();
+      cells = feed_add_cells(f.addParticle, f.addParticleBox, f.eccentricity, all, f.reduceNumberFactor);
+      double lo[3], hi[3];
+      int per[3];
+      e.box(lo, hi, per);
+      for (int c : cells) {
+        const double* p = &all[3 * (size_t)c];
+        if ((int)f.addParticleInfo[2] == 1 && f.deleteParticle > 0 &&
+            point_in_region(f.addParticle, f.deleteParticleBox, f.eccentricity, p[0], p[1], p[2]))
+          fail("%s: the centre of add cell %d lies inside deleteParticleBox and addParticleInfo's type is 1: the grain "
+               "would be created and deleted in the same step", who, c);
+        for (int k = 0; k < 3; k++)
+          if (!per[k] && (p[k] - 0.5 * f.randomPerturb < lo[k] || p[k] + 0.5 * f.randomPerturb > hi[k]))
+            fail("%s: add cell %d: centre %g +- randomPerturb / 2 = %g leaves the box [%g, %g] along axis %d, which is not "
+                 "periodic", who, c, p[k], 0.5 * f.randomPerturb, lo[k], hi[k], k);
+        cc.insert(cc.end(), p, p + 3);
+      }
+    }
+    if (feed_centres_) SF_HIP(hipFree(feed_centres_));
+    feed_centres_ = nullptr;
+    if (!cc.empty()) {
+      SF_HIP(hipMalloc(&feed_centres_, sizeof(double) * cc.size()));
+      SF_HIP(hipMemcpy(feed_centres_, cc.data(), sizeof(double) * cc.size(), hipMemcpyHostToDevice));
+    }
+    feed_ = f;
+    feed_cells_ = cells;
+    if (f.addParticle && !props_.addParticleOption) props_.addParticleOption = f.addParticle;   // one variable (:450)
+    timeToAdd_ = f.addParticle > 0 ? f.addParticleTimeStep : 1.0 / kRootVSmall;   // softParticleCloud.C:472, :477-482
+    totalAdd_ = totalDelete_ = totalDeleteBeforeAdd_ = 0;
+    lastAdd_ = lastDelete_ = lastDeleteBeforeAdd_ = 0;
+    feed_on_ = f.addParticle > 0 || f.deleteParticle > 0;
+  }
+
+  // One sub-cycle of the schedules: the net effect of enhancedCloud.C:698-711 followed by addAndDeleteParticle
+  // (softParticleCloud.C:1206-1268).  The sequence is the host's: clear, create, delete, a rebuild behind each that changed
+  // something.
+  void feed_step()
+  {
+    if (!feed_on_) return;
+    const sf_cloud_feed& f = feed_;
+    DemEngine& e = lmp_->eng;
+    lastAdd_ = lastDelete_ = lastDeleteBeforeAdd_ = 0;
+    const bool add_due = f.addParticle > 0 && timeToAdd_ <= 0.0;
+    const bool del = f.deleteParticle > 0;
+    if (!add_due) timeToAdd_ -= deltaT_;
+    // (region kind 0: pointInRegion is false everywhere, deleteParticle alone removes nothing)
+    if (!add_due && !(del && f.addParticle > 0)) return;
+    FeedMark m;
+    m.option = f.addParticle;
+    m.clear = (add_due && f.deleteBeforeAdd && del) ? 1 : 0;   // deleteParticleBeforeAdd is empty with deleteParticle 0 (:1088)
+    m.del = del ? 1 : 0;
+    m.flag_cleared = add_due ? 1 : 0;
+    m.tag_limit = INT_MAX;
+    for (int k = 0; k < 9; k++) {
+      m.clearBox[k] = f.clearInitialBox[k];
+      m.deleteBox[k] = f.deleteParticleBox[k];
+    }
+    for (int k = 0; k < 3; k++) m.ecc[k] = f.eccentricity[k];
+    const int n_before = e.nlocal();
+    const FeedCounts c = e.feed_mark(m);
+    if (!add_due && !c.deleted) return;
+    const char* who = "the cloud's add / delete schedules";
+    int added = add_due ? (int)feed_cells_.size() : 0;   // (none: addParticleBox holds no cell centre, a drain-only case)
+    if (c.cleared || added || c.deleted) particles_change_begin(*lmp_, who, added > 0);
+    if (add_due) {
+      if (c.cleared) {
+        e.compact_marked(c.cleared);
+        particles_deleted_end(*lmp_);
+      }
+      if (added) {
+        FeedCreate fc;
+        fc.np = added;
+        fc.first_tag = c.maxtag + 1;   // enhancedCloud.C:1064: maxTag_ + 1 + i, maxTag_ found anew at every add
+        fc.type = (int)f.addParticleInfo[2];
+        fc.mask = e.created_mask();
+        fc.radius = 0.5 * f.addParticleInfo[0];
+        fc.mass = DemEngine::created_mass(f.addParticleInfo[0], f.addParticleInfo[1]);
+        for (int k = 0; k < 3; k++) fc.vel[k] = f.addParticleVelocity[k];
+        fc.perturb = f.randomPerturb;
+        // Random perturbation(size()): the cloud's size once its own lists are made (softParticleCloud.C:1183)
+        fc.seed = (uint64_t)(n_before - c.cleared + added - c.deleted);
+        fc.centres = feed_centres_;
+        e.feed_create(fc);
+        std::vector<double> tags(added);
+        for (int i = 0; i < added; i++) tags[i] = fc.first_tag + i;
+        particles_created_end(*lmp_, tags.data(), added);
+      }
+      totalDeleteBeforeAdd_ += c.cleared;
+      totalAdd_ += added;
+      timeToAdd_ = f.addParticleTimeStep;
+    }
+    if (c.deleted) {
+      // The first mark of a sub-cycle with an add due left the CLEARED grains in leave_ (flag_cleared), and the rebuilds
+      // above may have re-sorted the atoms: mark again for the delete, without the grains just made.  Also when nothing
+      // was cleared and nothing made (no add cell): leave_ is all zero then, not the delete flags.
+      if (add_due) {
+        m.clear = 0;
+        m.flag_cleared = 0;
+        m.tag_limit = c.maxtag;
+        const FeedCounts c2 = e.feed_mark(m);
+        if (c2.deleted != c.deleted) fail("%s: %d grains to delete before the add, %d after it", who, c.deleted, c2.deleted);
+      }
+      e.compact_marked(c.deleted);
+      particles_deleted_end(*lmp_);
+      totalDelete_ += c.deleted;
+    }
+    lastAdd_ = added;
+    lastDelete_ = c.deleted;
+    lastDeleteBeforeAdd_ = add_due ? c.cleared : 0;
+  }
+
+  void feed_info(sf_cloud_feed_stats* st) const
+  {
+    st->totalAdd = totalAdd_;
+    st->totalDelete = totalDelete_;
+    st->totalDeleteBeforeAdd = totalDeleteBeforeAdd_;
+    st->timeToAddParticle = feed_on_ || feed_.addParticle > 0 ? timeToAdd_ : 1.0 / kRootVSmall;
+    st->nAddCells = (int)feed_cells_.size();
+    st->lastAdd = lastAdd_;
+    st->lastDelete = lastDelete_;
+    st->lastDeleteBeforeAdd = lastDeleteBeforeAdd_;
+  }
+  const std::vector<int>& feed_cells() const { return feed_cells_; }
 
   int particle_count() const { return lmp_->eng.nlocal(); }
   void slab_info(void** lammps, int* n3, int* nx_global, int* periodic_x, int* smoothing)
@@ -1088,6 +1237,16 @@ public:
   double deltaT_;
   MeshDev mesh_{};
   double* faces_dev_[3] = {nullptr, nullptr, nullptr};
+  std::vector<double> faces_host_[3];   // (graded axes: the add cells' centres are found on the host)
+  // the add / delete schedules (set_feed): the keys, the add cells (labels; their centres on the device), the
+  // reference's timer and running totals (softParticleCloud.H: timeToAddParticle_, totalAdd_, ...)
+  bool feed_on_ = false, feed_phase_done_ = false;   // (the latter: phase 7 has run since the last phase 1)
+  sf_cloud_feed feed_{};
+  std::vector<int> feed_cells_;
+  double* feed_centres_ = nullptr;
+  double timeToAdd_ = 0.0;
+  long long totalAdd_ = 0, totalDelete_ = 0, totalDeleteBeforeAdd_ = 0;
+  int lastAdd_ = 0, lastDelete_ = 0, lastDeleteBeforeAdd_ = 0;
   std::vector<int> label_;   // grid cell -> OpenFOAM cell label (empty: identity)
   hipStream_t s_ = nullptr;
   int subCycles_ = 1, subSteps_ = 1;
@@ -1242,6 +1401,31 @@ int sf_cloud_get_timers(void* cloud, sf_cloud_timers* t)
   SF_API_BEGIN
   *t = static_cast<Cloud*>(cloud)->timers();
   SF_API_END(0)
+}
+
+int sf_cloud_set_feed(void* cloud, const sf_cloud_feed* feed)
+{
+  SF_API_BEGIN
+  if (!cloud || !feed) sf::fail("sf_cloud_set_feed: null argument");
+  static_cast<Cloud*>(cloud)->set_feed(*feed);
+  SF_API_END(0)
+}
+
+int sf_cloud_feed_info(void* cloud, sf_cloud_feed_stats* stats)
+{
+  SF_API_BEGIN
+  if (!cloud || !stats) sf::fail("sf_cloud_feed_info: null argument");
+  static_cast<Cloud*>(cloud)->feed_info(stats);
+  SF_API_END(0)
+}
+
+int sf_cloud_feed_cells(void* cloud, int* cells, int cap)
+{
+  SF_API_BEGIN
+  if (!cloud) sf::fail("sf_cloud_feed_cells: null argument");
+  const std::vector<int>& c = static_cast<Cloud*>(cloud)->feed_cells();
+  for (int i = 0; cells && i < cap && i < (int)c.size(); i++) cells[i] = c[i];
+  SF_API_END((int)c.size())
 }
 
 int sfk_drag_model_jd(int model, int n, const double* Ur, const double* alpha, const double* pd, double nuf,

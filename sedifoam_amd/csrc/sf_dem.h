@@ -90,6 +90,10 @@ enum Flag {
   F_HALO_TIMEOUT_PEER,   // ... which rank's ...
   F_HALO_TIMEOUT_SEEN,   // ... and the value its flag had (adjacent words: brick_direct_probe clears the three together)
   F_PARK_OVER,      // list build: most accepted candidates of an atom when they did not fit the parking rows in LDS (BuildParams::P)
+  // the cloud's add / delete schedules (k_feed_mark, sf_feed.hip): adjacent words, DemEngine::feed_mark clears the three together
+  F_FEED_CLEARED,   // type-1 grains inside clearInitialBox
+  F_FEED_DELETED,   // type-1 grains inside deleteParticleBox that were not cleared
+  F_FEED_MAXTAG,    // largest tag among the grains not cleared
   F_ARRIVAL = 31,   // host side only: "the copy of this block has landed" (DemEngine::flags_copy_wait); never written on the device
   F_NFLAGS = 32
 };
@@ -456,6 +460,16 @@ class DemEngine {
   void create_particles(int np, const double* pos, const double* tag, double diameter, double rho,
                         int type, const double* vel);
   void delete_particles(const int* tags, int n);
+  // ---- the cloud's add / delete schedules (sf_feed.h, sf_feed.hip; single domain) ----
+  // One launch over the owned atoms: leave_ written on the device, the grains cleared / deleted counted and the largest tag
+  // among the grains not cleared found, three integers read back with the flag words.
+  struct FeedCounts feed_mark(const struct FeedMark& m);
+  // the second half of delete_particles, from flags that are on the device already: `ndel` non-zero words in leave_
+  void compact_marked(int ndel);
+  // create_particles with every row of the new atoms written by one launch (positions: cell centre + perturbation)
+  void feed_create(const struct FeedCreate& c);
+  int created_mask() const;                              // mask and mass of a created atom (library.cpp:452-460)
+  static double created_mass(double diameter, double rho);
 
   // halo (device buffers)
   long long border_pack(int side, double xshift, double* buf, long long max_atoms);
@@ -684,6 +698,8 @@ private:
   };
   void permute_locals(const int* perm, int n_new, bool rows = true, const RankJob* rank = nullptr);
   void migrate_compact();
+  bool create_rows_begin(int np, double r);         // the two halves of create_particles around the writing of the rows
+  void create_rows_end(int np, bool stage_first);
   void compute_partner_tags(bool allow_in_place = true);
   int select_locals(int mode, double bound, DevArray& list, int dim = 0);
  public:

@@ -1182,18 +1182,11 @@ void DemEngine::create_particles(int np, const double* pos, const double* tag, d
                                  const double* vel)
 {
   if (np <= 0) return;
-  ensure_capacity((size_t)nlocal_ + nghost_ + np + 1024);
   const double r = 0.5 * diameter;
-  // library.cpp:460 -- the reference's mistyped pi literal is kept
-  const double m = 4.0 * kPiTypo / 3.0 * r * r * r * rho;
+  const bool stage_first = create_rows_begin(np, r);
+  const double m = created_mass(diameter, rho);
   std::vector<double4> hx(np), hv(np), hw(np, double4{0, 0, 0, 0}), hz(np, double4{0, 0, 0, 0});
-  // library.cpp:452-455: mask = 1 | bitmask of group "active" (the reference indexes bitmask[-1] when the group does
-  // not exist; here the new atoms are then in `all` only)
-  int newmask = 1;
-  {
-    auto it = groups_.find("active");
-    if (it != groups_.end()) newmask |= it->second;
-  }
+  const int newmask = created_mask();
   std::vector<int> ht(np), hty(np, type), hm(np, newmask), h0(np, 0);
   for (int k = 0; k < np; k++) {
     hx[k] = {pos[3 * k], pos[3 * k + 1], pos[3 * k + 2], r};
@@ -1201,13 +1194,6 @@ void DemEngine::create_particles(int np, const double* pos, const double* tag, d
     ht[k] = (int)tag[k];  // library.cpp:437
     max_tag_ = std::max(max_tag_, ht[k]);
   }
-  rmax_ = std::max(rmax_, r);
-  // Words that index ghost SLOTS (the LDS-staged form; the other forms name a root and an image code): the new atoms take
-  // the slots of the first ghosts, and with them the tags the old list's history is found by -- the copy of an
-  // owned-ghost pair on the owned side lost its history, unseen by get_history where the other side has the lower tag.
-  // Stage the history by partner tag while the ghosts are still there.
-  const bool stage_first = setup_done_ && !have_subdomain_ && have_list_ && !roots_ && nghost_ > 0;
-  if (stage_first) compute_partner_tags(/*allow_in_place=*/false);
   // ghosts are dropped (library.cpp:476-480 resets nghost) and re-created by the forced rebuild below
   const size_t o4 = sizeof(double4) * nlocal_, oi = sizeof(int) * nlocal_;
   auto up = [&](DevArray& a, const void* src, size_t bytes, size_t off) {
@@ -1239,6 +1225,44 @@ void DemEngine::create_particles(int np, const double* pos, const double* tag, d
     up(extra_, iv.data(), sizeof(double) * np, sizeof(double) * ((size_t)r * cap_ + nlocal_));
     sync();
   }
+  create_rows_end(np, stage_first);
+}
+
+// library.cpp:452-455: mask = 1 | bitmask of group "active" (the reference indexes bitmask[-1] when the group does
+// not exist; here the new atoms are then in `all` only)
+int DemEngine::created_mask() const
+{
+  int newmask = 1;
+  auto it = groups_.find("active");
+  if (it != groups_.end()) newmask |= it->second;
+  return newmask;
+}
+
+// library.cpp:460 -- the reference's mistyped pi literal is kept
+double DemEngine::created_mass(double diameter, double rho)
+{
+  const double r = 0.5 * diameter;
+  return 4.0 * kPiTypo / 3.0 * r * r * r * rho;
+}
+
+// create_particles in two halves around the writing of the new atoms' rows at offset nlocal_ (uploads there, one kernel in
+// DemEngine::feed_create): room for them and, where the old list needs it, its history staged ...
+bool DemEngine::create_rows_begin(int np, double r)
+{
+  ensure_capacity((size_t)nlocal_ + nghost_ + np + 1024);
+  rmax_ = std::max(rmax_, r);
+  // Words that index ghost SLOTS (the LDS-staged form; the other forms name a root and an image code): the new atoms take
+  // the slots of the first ghosts, and with them the tags the old list's history is found by -- the copy of an
+  // owned-ghost pair on the owned side lost its history, unseen by get_history where the other side has the lower tag.
+  // Stage the history by partner tag while the ghosts are still there.
+  const bool stage_first = setup_done_ && !have_subdomain_ && have_list_ && !roots_ && nghost_ > 0;
+  if (stage_first) compute_partner_tags(/*allow_in_place=*/false);
+  return stage_first;
+}
+
+// ... and, the rows written and max_tag_ raised: the image counts of the new tags, the new atom count, the forced rebuild
+void DemEngine::create_rows_end(int np, bool stage_first)
+{
   if (image_) {   // a created atom starts in image 0, whatever an earlier holder of its tag had counted
     images_fit();
     k_image_zero<<<div_up(np, 256), 256, 0, stream_>>>(tag_.as<int>() + nlocal_, np, image_, (int)image_rows_);
@@ -1275,11 +1299,19 @@ void DemEngine::delete_particles(const int* tags, int n)
       ndel++;
     }
   if (!ndel) return;
+  SF_HIP(hipMemcpyAsync(leave_.ptr, leave.data(), sizeof(int) * nlocal_, hipMemcpyHostToDevice, stream_));
+  compact_marked(ndel);
+}
+
+// the second half of delete_particles: leave_ holds a non-zero word for each of the `ndel` owned atoms that go (written by
+// the upload above, or on the device by the cloud's mark kernel, sf_feed.hip)
+void DemEngine::compact_marked(int ndel)
+{
+  if (ndel <= 0 || !nlocal_) return;
   if (have_list_) {
     // the history of the surviving atoms must outlive the compaction: staged by partner tag, never read in place
     compute_partner_tags(/*allow_in_place=*/false);
   }
-  SF_HIP(hipMemcpyAsync(leave_.ptr, leave.data(), sizeof(int) * nlocal_, hipMemcpyHostToDevice, stream_));
   migrate_leavers_ = ndel;
   migrate_compact();
   nghost_ = 0;

@@ -21,6 +21,7 @@
 #include "sf_contacts.h"
 #include "sf_dump.h"
 #include "sf_env.h"
+#include "sf_feed.h"
 #include "sf_global.h"
 #include "sf_histo.h"
 #include "sf_restart.h"
@@ -210,6 +211,38 @@ void recount_atoms(SfLammps& L)
   if (L.decomposed && sf_slab_allreduce_sum(&L, &n, 1) != 0) sf::fail("%s", sf::last_error().c_str());
   L.natoms = (long long)n;
 }
+
+}  // namespace
+
+// What lammps_create_particle / lammps_delete_particle do around the engine call; the cloud's add / delete schedules
+// (sf_cloud.hip, sf_feed.h) go through the same three functions.
+namespace sf {
+void particles_change_begin(SfLammps& L, const char* who, bool creating)
+{
+  if (L.eng.rigid_on()) fail("%s: not while fix rigid/nve exists (its bodies are fixed sets of atoms)", who);
+  atom_compute_invalidate(L);
+  if (creating && L.world_size == 1 && !L.decomposed && !L.eng.decomposed()) (void)L.eng.images_enable();
+}
+
+void particles_created_end(SfLammps& L, const double* tags, int np)
+{
+  displace_created(L, tags, np);   // (the displacement computes: the new atoms' reference is where they are now)
+  if (L.decomposed) {   // library.cpp:470-473 (collective: every rank calls, possibly with npAdd = 0)
+    recount_atoms(L);
+    L.pending_rebuild = true;
+  }
+}
+
+void particles_deleted_end(SfLammps& L)
+{
+  if (L.decomposed) {   // library.cpp:527-537: collective counts; every rank deletes the listed atoms it owns
+    recount_atoms(L);
+    L.pending_rebuild = true;
+  }
+}
+}  // namespace sf
+
+namespace {
 
 void read_data(SfLammps& L, const std::string& path, bool molecules = false)
 {
@@ -956,15 +989,9 @@ int sf_lammps_create_particle(void* ptr, int npAdd, const double* position, cons
 {
   SF_API_BEGIN
   SfLammps* L = H(ptr);
-  if (L->eng.rigid_on()) sf::fail("lammps_create_particle: not while fix rigid/nve exists (its bodies are fixed sets of atoms)");
-  sf::atom_compute_invalidate(*L);
-  if (L->world_size == 1 && !L->decomposed && !L->eng.decomposed()) (void)L->eng.images_enable();
+  sf::particles_change_begin(*L, "lammps_create_particle", true);
   L->eng.create_particles(npAdd, position, tag, diameter, rho, type, vel);
-  sf::displace_created(*L, tag, npAdd);   // (the displacement computes: the new atoms' reference is where they are now)
-  if (L->decomposed) {   // library.cpp:470-473 (collective: every rank calls, possibly with npAdd = 0)
-    recount_atoms(*L);
-    L->pending_rebuild = true;
-  }
+  sf::particles_created_end(*L, tag, npAdd);
   SF_API_END(0)
 }
 
@@ -972,13 +999,9 @@ int sf_lammps_delete_particle(void* ptr, const int* deleteList, int nDelete)
 {
   SF_API_BEGIN
   SfLammps* L = H(ptr);
-  if (L->eng.rigid_on()) sf::fail("lammps_delete_particle: not while fix rigid/nve exists (its bodies are fixed sets of atoms)");
-  sf::atom_compute_invalidate(*L);
+  sf::particles_change_begin(*L, "lammps_delete_particle", false);
   L->eng.delete_particles(deleteList, nDelete);
-  if (L->decomposed) {   // library.cpp:527-537: collective counts; every rank deletes the listed atoms it owns
-    recount_atoms(*L);
-    L->pending_rebuild = true;
-  }
+  sf::particles_deleted_end(*L);
   SF_API_END(0)
 }
 
