@@ -194,6 +194,26 @@ int sf_lammps_global_launches(void *ptr, long long *launches, long long *host_co
 /* measurement (tools/global_cost.py): GPU ms of one fresh evaluation of global compute `id` now, from HIP events (the
  * per-atom computes behind its c_ inputs are evaluated before the clock starts) */
 int sf_lammps_global_cost(void *ptr, const char *id, double *ms);
+/* rows of `fix ID group ave/time ... c_ID[k] ... mode vector` (the columns of global arrays with one row count, such as
+ * compute rdf): sf_lammps_ave_time then returns rows x nvalues values, row-major.  0 for a mode scalar fix; -1 on error */
+long long sf_lammps_ave_time_rows(void *ptr, const char *id);
+/* the neighbourhood walk on a grid of the user's cutoff (the script commands `compute ID group rdf Nbin [itype jtype ...]
+ * cutoff Rc`, a global array, and `compute ID group coord/atom cutoff Rc [typerange ...]`, a per-atom compute behind
+ * sf_lammps_compute_atom), on the positions as they stand.  The global array of compute rdf `id`: Nbin rows of 1 + 2 npairs
+ * columns, row-major -- the bin centre, then g(r) and the running coordination number of each pair.  *ncols (may be NULL)
+ * the columns.  Returns rows x columns, or -1 (sf_last_error); with max smaller than that nothing is evaluated or written.
+ * Passive: the run goes on with the same bits. */
+long long sf_lammps_compute_array(void *ptr, const char *id, long long max, double *values, int *ncols);
+/* the raw 64-bit counts of compute rdf `id`: counts [npairs][Nbin] ordered pairs, per_pair [npairs][3] = icount jcount
+ * duplicates (the group atoms in a pair's itype range, jtype range and both).  Returns npairs x Nbin, or -1; with max smaller
+ * than that nothing is evaluated or written */
+long long sf_lammps_rdf_counts(void *ptr, const char *id, long long max, long long *counts, long long *per_pair, int *npairs);
+/* cutoff grids built, kernel launches made and device-to-host copies made for compute rdf and coord/atom so far (all 0 for
+ * a run that evaluates neither) */
+int sf_lammps_nbr_launches(void *ptr, long long *grid_builds, long long *launches, long long *host_copies);
+/* measurement (tools/nbr_cost.py): GPU ms from HIP events of one fresh grid build and of one walk of compute `id` (rdf or
+ * coord/atom) now */
+int sf_lammps_nbr_cost(void *ptr, const char *id, double *grid_ms, double *walk_ms);
 /* unwrapped coordinates (the attributes xu yu zu ix iy iz of `compute property/atom`, `compute ID group displace/atom`,
  * `compute ID group com`): the engine counts, per tag, how many box
  * lengths the periodic wrap has taken an atom back by.  out[3 * nlocal]: ix iy iz of the owned atoms in the atom order

@@ -138,6 +138,11 @@ _SIGS = {
     "sf_lammps_ave_time_names": (C.c_longlong, [vp, C.c_char_p, C.c_longlong, C.c_char_p]),
     "sf_lammps_global_launches": (C.c_int, [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "sf_lammps_global_cost": (C.c_int, [vp, C.c_char_p, dp]),
+    "sf_lammps_ave_time_rows": (C.c_longlong, [vp, C.c_char_p]),
+    "sf_lammps_compute_array": (C.c_longlong, [vp, C.c_char_p, C.c_longlong, dp, ip]),
+    "sf_lammps_rdf_counts": (C.c_longlong, [vp, C.c_char_p, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), ip]),
+    "sf_lammps_nbr_launches": (C.c_int, [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "sf_lammps_nbr_cost": (C.c_int, [vp, C.c_char_p, dp, dp]),
     "sf_lammps_get_image": (C.c_int, [vp, ip]),
     "sf_lammps_region_match": (C.c_int, [vp, C.c_char_p, C.c_int, dp, ip]),
     "sf_lammps_group_mask": (C.c_int, [vp, C.c_char_p, ip]),

@@ -13,7 +13,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # per-file flags.  sf_dem.hip (the sub-step kernel): the ILP-first machine scheduler orders the loop's loads and the FP64
 # chains so that the kernel runs 1.7-1.9 % faster at 1 M grains on three boxes (2.7 % at 2 M, neutral below 130 k; same
 # registers, no scratch; results bit-identical) -- profiles/r04_README.md section 3
-FILE_FLAGS = {"sf_dem.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
+FILE_FLAGS = {"sf_dem.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
+              # sf_nbr.hip (the cutoff-grid walk): every product and sum of a squared distance and of the rdf normalisation
+              # is rounded on its own, so that compute rdf and coord/atom equal their NumPy statement bit for bit
+              "sf_nbr.hip": ["-ffp-contract=off"]}
 
 
 def _sources():

@@ -35,6 +35,7 @@
 #include "sf_compute_atom.h"
 #include "sf_contacts.h"
 #include "sf_global.h"
+#include "sf_nbr.h"
 
 namespace sf {
 namespace {
@@ -343,7 +344,7 @@ bool per_atom_value(int source) { return source != AS_DENSITY_NUMBER && source !
 void check_compute_value(const SfLammps& L, const AveValue& v)
 {
   const int nc = atom_compute_ncols(L, v.id);
-  if (nc == 0 && (pair_local_exists(L, v.id) || global_compute_nvalues(L, v.id) > 0))
+  if (nc == 0 && (pair_local_exists(L, v.id) || global_compute_nvalues(L, v.id) > 0 || rdf_array_rows(L, v.id) > 0))
     fail("Fix ave/chunk compute does not calculate per-atom values");
   if (nc == 0) fail("Compute ID for fix ave/chunk does not exist");
   if (v.index == 0 && nc != 1) fail("Fix ave/chunk compute does not calculate a per-atom vector");
@@ -606,7 +607,8 @@ void ave_chunk_fix_command(SfLammps& L, const std::string& line)
     fail("fix ave/chunk %s: this fix ID is in use (unfix it first)", F->S.id.c_str());
   ChunkCompute* c = T.find(F->S.chunk);
   if (!c) {
-    if (atom_compute_ncols(L, F->S.chunk) > 0 || pair_local_exists(L, F->S.chunk) || global_compute_nvalues(L, F->S.chunk) > 0)
+    if (atom_compute_ncols(L, F->S.chunk) > 0 || pair_local_exists(L, F->S.chunk) || global_compute_nvalues(L, F->S.chunk) > 0 ||
+        rdf_array_rows(L, F->S.chunk) > 0)
       fail("Fix ave/chunk does not use chunk/atom compute");
     fail("Chunk/atom compute does not exist for fix ave/chunk");
   }

@@ -7,6 +7,8 @@
 #include <string>
 #include <vector>
 
+#include "sf_nbr_parse.h"
+
 namespace sf {
 struct SfLammps;
 
@@ -26,6 +28,9 @@ void atom_compute_invalidate(SfLammps& L);
 long long atom_compute_launches(const SfLammps& L);
 // GPU time from HIP events of one fresh evaluation of `id` (tools/compute_atom_cost.py)
 double atom_compute_cost(SfLammps& L, const std::string& id);
+// compute coord/atom `id`: its group bit, cutoff and type ranges (sf_lammps_nbr_cost times its grid and walk); false: no
+// compute coord/atom has this ID
+bool atom_compute_coord_spec(const SfLammps& L, const std::string& id, int* groupbit, double* rc, std::vector<TypeRange>* ranges);
 // compute displace/atom: is there one, and lammps_create_particle has made atoms with the tags d_tags[0 .. np) (device) --
 // where they are now is their reference (displace_created of sf_displace.hip calls both)
 bool atom_compute_tracks_created(const SfLammps& L);

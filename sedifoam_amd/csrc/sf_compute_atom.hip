@@ -14,6 +14,9 @@
 //                                          image counts (sf_unmap.h).  One attribute a per-atom vector, several an array
 //   compute ID group displace/atom         dx dy dz and their length: unmap(x) - x0, x0 the unwrapped position when the
 //                                          compute was defined (of an atom created later: at its creation); DESIGN.md 17
+//   compute ID group coord/atom cutoff Rc [typerange ...]   the atoms j != i (of any group) with rsq < Rc^2, per type range:
+//                                          a walk of a grid of that cutoff on the positions as they stand (sf_nbr.hip;
+//                                          DESIGN.md 20), not of the pair list.  One range a vector, several an array
 // The group selects the atoms that get a value; atoms outside it read 0.  Like compute pair/local (sf_contacts.hip) a
 // value is evaluated from the state AT THE MOMENT OF THE OUTPUT -- the x v omega a dump custom frame shows, the shear
 // history sf_dem_get_history returns -- with shearupdate = false, and nothing is stored back.  (LAMMPS tallies vatom inside
@@ -41,6 +44,7 @@
 #include "sf_global.h"
 #include "sf_global_parse.h"
 #include "sf_handles.h"
+#include "sf_nbr.h"
 
 namespace sf {
 namespace {
@@ -252,10 +256,10 @@ __global__ __launch_bounds__(256) void k_atom_displace(const double4* xr, const 
 
 // ---- host side ----
 
-enum Kind { K_STRESS, K_CONTACT, K_KE, K_EROTATE, K_PROPERTY, K_DISPLACE };
-constexpr int kNumKinds = 6;
+enum Kind { K_STRESS, K_CONTACT, K_KE, K_EROTATE, K_PROPERTY, K_DISPLACE, K_COORD };
+constexpr int kNumKinds = 7;
 const char* const kStyleName[kNumKinds] = {"stress/atom", "contact/atom", "ke/atom", "erotate/sphere/atom", "property/atom",
-                                           "displace/atom"};
+                                           "displace/atom", "coord/atom"};
 
 struct Grown {   // device scratch, grown geometrically (no allocation per frame once it has grown)
   void* p = nullptr;
@@ -285,11 +289,16 @@ struct AtomCompute {
   bool ke = true, pair = true;
   std::vector<int> attrs;   // K_PROPERTY
   RefTable ref;             // K_DISPLACE: the reference positions, by tag
+  CoordSpec coord;          // K_COORD: the cutoff and the type ranges
   Grown val;
   // what the buffer was made at (-1: nothing)
   long long step = -1, nbuilds = -1;
   int nlocal = -1;
-  int ncols() const { return kind == K_STRESS ? 6 : (kind == K_PROPERTY ? (int)attrs.size() : (kind == K_DISPLACE ? 4 : 1)); }
+  int ncols() const
+  {
+    if (kind == K_COORD) return (int)coord.ranges.size();
+    return kind == K_STRESS ? 6 : (kind == K_PROPERTY ? (int)attrs.size() : (kind == K_DISPLACE ? 4 : 1));
+  }
   bool needs_image() const
   {
     if (kind == K_DISPLACE) return true;
@@ -349,7 +358,9 @@ void evaluate(SfLammps& L, AtomSet& T, AtomCompute& c)
   const int n = e.nlocal();
   hipStream_t st = e.stream();
   double* val = static_cast<double*>(c.val.get(sizeof(double) * (size_t)c.ncols() * (size_t)std::max(n, 1), st));
-  if (n > 0) {
+  if (c.kind == K_COORD) {   // (the grid and the walk are launches of sf_nbr.hip, counted there)
+    nbr_coord_atom(L, "compute coord/atom", c.groupbit, c.coord.rc, c.coord.ranges, val);
+  } else if (n > 0) {
     const unsigned nb = (unsigned)div_up(n, 256);
     if (c.kind == K_KE || c.kind == K_EROTATE) {
       k_atom_kinetic<<<nb, 256, 0, st>>>(e.d_xr(), e.d_vm(), e.d_om(), e.d_mask(), c.groupbit, c.kind == K_EROTATE ? 1 : 0, n,
@@ -423,6 +434,9 @@ void atom_compute_define(SfLammps& L, const std::vector<std::string>& w)
   } else if (c->kind == K_DISPLACE) {
     const std::string err = parse_displace_atom(w);
     if (!err.empty()) fail("%s", err.c_str());
+  } else if (c->kind == K_COORD) {
+    const std::string err = parse_coord_atom(w, &c->coord);
+    if (!err.empty()) fail("%s", err.c_str());
   } else if (w.size() != 4)
     fail("Illegal compute %s command", w[3].c_str());
   refuse_unsupported(L, c->kind);
@@ -463,6 +477,8 @@ const double* atom_compute_values(SfLammps& L, const std::string& id, int* ncols
     return chunk_compute_values(L, id);
   }
   if (!c && global_compute_nvalues(L, id) > 0) fail("compute %s does not calculate per-atom values (it is a global compute)", id.c_str());
+  if (!c && rdf_array_rows(L, id) > 0)
+    fail("compute %s does not calculate per-atom values (it is a global array: sf_lammps_compute_array returns it)", id.c_str());
   if (!c) fail("Could not find compute ID %s", id.c_str());
   const DemEngine& e = L.eng;
   if (c->step != e.nsteps() || c->nbuilds != e.nbuilds() || c->nlocal != e.nlocal()) evaluate(L, *T, *c);
@@ -475,8 +491,20 @@ void atom_compute_invalidate(SfLammps& L)
 {
   chunk_invalidate(L);
   global_invalidate(L);
+  nbr_invalidate(L);
   if (AtomSet* T = set_of(L))
     for (auto& c : T->computes) c->step = -1;
+}
+
+bool atom_compute_coord_spec(const SfLammps& L, const std::string& id, int* groupbit, double* rc, std::vector<TypeRange>* ranges)
+{
+  AtomSet* T = set_of(L);
+  const AtomCompute* c = T ? T->find(id) : nullptr;
+  if (!c || c->kind != K_COORD) return false;
+  *groupbit = c->groupbit;
+  *rc = c->coord.rc;
+  *ranges = c->coord.ranges;
+  return true;
 }
 
 bool atom_compute_tracks_created(const SfLammps& L)

@@ -39,6 +39,7 @@
 #include "sf_dem_dispatch.h"
 #include "sf_dump_fmt.h"
 #include "sf_global.h"
+#include "sf_nbr.h"
 #include "sf_ave_fix.h"
 #include "sf_thermo.h"
 
@@ -318,10 +319,15 @@ bool compute_command(SfLammps& L, const std::vector<std::string>& w)
     Compute* c = S ? S->find(w[1]) : nullptr;
     const bool per_atom = !c && atom_compute_ncols(L, w[1]) > 0;   // (one ID space: sf_compute_atom.hip holds the others)
     const bool global = !c && !per_atom && global_compute_nvalues(L, w[1]) > 0;   // (sf_global.hip holds those)
-    if (!c && !per_atom && !global) fail("Could not find compute ID to delete");   // [3P] Modify::delete_compute
+    const bool array = !c && !per_atom && !global && rdf_array_rows(L, w[1]) > 0;   // (sf_nbr.hip holds compute rdf)
+    if (!c && !per_atom && !global && !array) fail("Could not find compute ID to delete");   // [3P] Modify::delete_compute
     if (reduce_uses_compute(L, w[1])) fail("uncompute %s: a compute reduce still uses this compute (uncompute it first)", w[1].c_str());
     if (const char* who = ave_fix_uses_compute(L, w[1]))
       fail("uncompute %s: a %s still uses this compute (unfix it first)", w[1].c_str(), who);
+    if (array) {
+      rdf_compute_remove(L, w[1]);
+      return true;
+    }
     if (global) {
       if (thermo_uses_compute(L, w[1]))
         fail("uncompute %s: thermo_style custom still names this compute (give another thermo_style first)", w[1].c_str());
@@ -344,16 +350,22 @@ bool compute_command(SfLammps& L, const std::vector<std::string>& w)
     fail("compute cohe/local is not built (fix cohesive is a fix and has no single(); the reference's own code behind it "
          "never terminates)");
   const bool per_atom = atom_compute_style(style), global = global_compute_style(style);
-  if (style != "pair/local" && style != "gran/local" && !per_atom && !global)
+  const bool array = rdf_compute_style(style);
+  if (style != "pair/local" && style != "gran/local" && !per_atom && !global && !array)
     fail("Invalid compute style %s (this engine has compute pair/local, also under the name gran/local, the per-atom "
          "computes stress/atom, contact/atom, ke/atom, erotate/sphere/atom, property/atom and chunk/atom, and the global "
          "computes reduce, ke and erotate/sphere; on unwrapped coordinates the per-atom compute displace/atom and the global "
-         "compute com)", style.c_str());
+         "compute com; on a grid of the user's cutoff the global array rdf and the per-atom compute coord/atom)", style.c_str());
   Compute c;
   c.id = w[1];
   c.groupbit = L.eng.group_bit(w[2]);
-  if ((set_of(L) && set_of(L)->find(c.id)) || atom_compute_ncols(L, c.id) > 0 || global_compute_nvalues(L, c.id) > 0)
+  if ((set_of(L) && set_of(L)->find(c.id)) || atom_compute_ncols(L, c.id) > 0 || global_compute_nvalues(L, c.id) > 0 ||
+      rdf_array_rows(L, c.id) > 0)
     fail("Reuse of compute ID");
+  if (array) {
+    rdf_compute_define(L, w);   // (sf_nbr.hip)
+    return true;
+  }
   if (global) {
     global_compute_define(L, w);   // (sf_global.hip)
     return true;
@@ -394,6 +406,8 @@ void compute_lookup(const SfLammps& L, const std::string& id, std::vector<unsign
     fail("Dump local compute does not compute local info: %s is a per-atom compute (dump custom prints it)", id.c_str());
   if (!c && global_compute_nvalues(L, id) > 0)
     fail("Dump local compute does not compute local info: %s is a global compute (fix ave/time and thermo print it)", id.c_str());
+  if (!c && rdf_array_rows(L, id) > 0)
+    fail("Dump local compute does not compute local info: %s is a global array (fix ave/time mode vector prints it)", id.c_str());
   if (!c) fail("Could not find dump local compute ID %s", id.c_str());
   if (values) *values = c->values;
   if (groupbit) *groupbit = c->groupbit;

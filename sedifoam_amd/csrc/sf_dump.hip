@@ -41,6 +41,7 @@
 #include "sf_dump.h"
 #include "sf_dump_fmt.h"
 #include "sf_global.h"
+#include "sf_nbr.h"
 #include "sf_handles.h"
 
 namespace sf {
@@ -586,6 +587,9 @@ void dump_command(SfLammps& L, const std::vector<std::string>& w)
                  "rows)", id.c_str());
       if (nc == 0 && global_compute_nvalues(L, id) > 0)
         sf::fail("Dump custom compute does not compute per-atom info: %s is a global compute (fix ave/time and thermo print it)",
+                 id.c_str());
+      if (nc == 0 && rdf_array_rows(L, id) > 0)
+        sf::fail("Dump custom compute does not compute per-atom info: %s is a global array (fix ave/time mode vector prints it)",
                  id.c_str());
       if (nc == 0) sf::fail("Could not find dump custom compute ID %s", id.c_str());
       if (idx == 0 && nc != 1) sf::fail("Dump custom compute does not compute per-atom vector: %s", w[k].c_str());

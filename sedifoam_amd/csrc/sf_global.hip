@@ -8,6 +8,9 @@
 //                                             over the columns of a compute displace/atom)
 //   fix ID group ave/time Nevery Nrepeat Nfreq c_ID c_ID[k] ... [ave one|running|window M] [start N] [file F] [overwrite]
 //       [format S] [title1 S] [title2 S]       time averages of global values, one line per Nfreq steps
+//       ... c_ID[k] ... mode vector [title3 S]   the columns of global arrays of one row count (compute rdf, sf_nbr.hip): a
+//                                             device accumulator [rows][values], k_global_col_acc per column and sample,
+//                                             one block of `row value ...` lines per Nfreq steps
 // A value is evaluated from the state AT THE MOMENT OF THE OUTPUT, like a dump frame, and stores nothing back into the run.
 //
 // One evaluation, on the engine's stream:
@@ -49,6 +52,7 @@
 #include "sf_gather_col.h"
 #include "sf_global.h"
 #include "sf_global_parse.h"
+#include "sf_nbr.h"
 
 // (a*a + s stays a product and a sum, so that a column's bits do not depend on what the compiler fuses around it)
 #pragma clang fp contract(off)
@@ -179,6 +183,14 @@ __global__ __launch_bounds__(kGBlock) void k_global_fold(const double* partial, 
   }
 }
 
+// fix ave/time mode vector: column `src` (stride ncols) of a global array is added into column j of the accumulator
+// [nrows][nv] -- one addition per element per sample
+__global__ __launch_bounds__(kGBlock) void k_global_col_acc(const double* src, int ncols, int nrows, double* acc, int nv)
+{
+  const int r = blockIdx.x * kGBlock + threadIdx.x;
+  if (r < nrows) acc[(size_t)r * nv] += src[(size_t)r * ncols];
+}
+
 __global__ __launch_bounds__(64) void k_global_acc(GAccOnly A)
 {
   const int t = threadIdx.x;
@@ -291,7 +303,16 @@ struct AveTimeFix : AveFixState {
   std::deque<std::vector<double>> blocks;   // ave window: the last M blocks
   std::vector<double> runsum;               // ave running: the sum of all blocks
   long long noutputs = 0;
-  std::vector<double> values;   // the latest output
+  std::vector<double> values;   // the latest output (mode vector: row-major [nrows][nvalues])
+  // mode vector: the columns of global arrays with nrows rows; the accumulator [nrows][nvalues] is an allocation of its own
+  int nrows = 0;
+  double* vacc = nullptr;
+  std::vector<double> h_vacc;
+  size_t nacc() const { return S.mode_vector ? (size_t)nrows * S.values.size() : S.values.size(); }
+  ~AveTimeFix()
+  {
+    if (vacc) (void)hipFree(vacc);
+  }
 };
 
 struct GlobalSet {
@@ -386,6 +407,9 @@ bool check_reduce_input(const SfLammps& L, const ReduceInput& in)
   }
   if (global_compute_nvalues(L, in.id) > 0)
     fail("Compute reduce compute calculates global values (c_%s is a global compute: per-atom and local ones are reduced)",
+         in.id.c_str());
+  if (rdf_array_rows(L, in.id) > 0)
+    fail("Compute reduce compute calculates global values (c_%s is a global array: per-atom and local ones are reduced)",
          in.id.c_str());
   fail("Compute ID for compute reduce does not exist");
 }
@@ -611,7 +635,7 @@ void check_fix_value(const SfLammps& L, const AveTimeValue& v)
   bool vec = false;
   const int n = global_compute_nvalues(L, v.id, &vec);
   if (n == 0) {
-    if (atom_compute_ncols(L, v.id) > 0 || pair_local_exists(L, v.id))
+    if (atom_compute_ncols(L, v.id) > 0 || pair_local_exists(L, v.id) || rdf_array_rows(L, v.id) > 0)
       fail(v.index == 0 ? "Fix ave/time compute does not calculate a scalar" : "Fix ave/time compute does not calculate a vector");
     fail("Compute ID for fix ave/time does not exist");
   }
@@ -620,25 +644,61 @@ void check_fix_value(const SfLammps& L, const AveTimeValue& v)
   if (v.index > n) fail("Fix ave/time compute vector is accessed out-of-range");
 }
 
+// mode vector: c_ID[k] is column k of a global array; every value of a fix has the same number of rows, which is returned.
+// Checked at the fix line and again at every sample
+int check_fix_column(const SfLammps& L, const AveTimeValue& v, int nrows)
+{
+  int ncols = 0;
+  const int rows = rdf_array_rows(L, v.id, &ncols);
+  if (rows == 0) {
+    if (global_compute_nvalues(L, v.id) > 0 || atom_compute_ncols(L, v.id) > 0 || pair_local_exists(L, v.id))
+      fail("Fix ave/time compute does not calculate an array");
+    fail("Compute ID for fix ave/time does not exist");
+  }
+  if (v.index > ncols) fail("Fix ave/time compute array is accessed out-of-range");
+  if (nrows > 0 && rows != nrows) fail("Fix ave/time columns must all be the same length");
+  return rows;
+}
+
 void write_line(AveTimeFix& F)
 {
   FILE* fp = F.file.fp();
   if (!fp) return;
   fail_if(F.file.begin_block());
-  fprintf(fp, "%lld", F.out_step);
-  for (double v : F.values) fprintf(fp, F.S.format.c_str(), v);
-  fputc('\n', fp);
+  if (F.S.mode_vector) {   // `step nrows`, then one line per row: the row number from 1 and its values
+    const size_t nv = F.S.values.size();
+    fprintf(fp, "%lld %d\n", F.out_step, F.nrows);
+    for (int r = 0; r < F.nrows; r++) {
+      fprintf(fp, "%d", r + 1);
+      for (size_t j = 0; j < nv; j++) fprintf(fp, F.S.format.c_str(), F.values[(size_t)r * nv + j]);
+      fputc('\n', fp);
+    }
+  } else {
+    fprintf(fp, "%lld", F.out_step);
+    for (double v : F.values) fprintf(fp, F.S.format.c_str(), v);
+    fputc('\n', fp);
+  }
   fail_if(F.file.end_block());
 }
 
 // the accumulator of Nrepeat samples -> one output (divided on the host)
 void make_output(SfLammps& L, GlobalSet& G, AveTimeFix& F)
 {
-  const int nv = (int)F.S.values.size();
-  copy_to_host(L, G, F.slot, nv, true);
+  const int nv = (int)F.nacc();
+  const double* h = G.h_buf;
+  if (F.S.mode_vector) {   // (its accumulator is larger than the pinned buffer of the scalar values)
+    hipStream_t st = L.eng.stream();
+    F.h_vacc.resize((size_t)nv);
+    SF_HIP(hipMemcpyAsync(F.h_vacc.data(), F.vacc, sizeof(double) * (size_t)nv, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipMemsetAsync(F.vacc, 0, sizeof(double) * (size_t)nv, st));
+    SF_HIP(hipStreamSynchronize(st));
+    G.host_copies++;
+    h = F.h_vacc.data();
+  } else
+    copy_to_host(L, G, F.slot, nv, true);
   std::vector<double> block(nv);
   const double nrep = (double)F.S.nrepeat;
-  for (int j = 0; j < nv; j++) block[j] = G.h_buf[j] / nrep;
+  for (int j = 0; j < nv; j++) block[j] = h[j] / nrep;
   F.noutputs++;
   F.values.assign(nv, 0.0);
   if (F.S.ave == AVE_ONE) F.values = block;
@@ -672,7 +732,7 @@ bool unfix(SfLammps& L, const std::string& id)
 {
   GlobalSet* G = set_of(L);
   const std::unique_ptr<AveTimeFix> f = G ? ave_take(L, G->fixes, id) : nullptr;
-  if (f) G->give(f->slot, (int)f->S.values.size());
+  if (f && !f->S.mode_vector) G->give(f->slot, (int)f->S.values.size());
   return f != nullptr;
 }
 
@@ -815,16 +875,26 @@ void ave_time_fix_command(SfLammps& L, const std::string& line)
   GlobalSet& G = ensure_set(L);
   if (ave_fix_exists(L, F->S.id))
     fail("fix ave/time %s: this fix ID is in use (unfix it first)", F->S.id.c_str());
-  for (const AveTimeValue& v : F->S.values) check_fix_value(L, v);
+  if (F->S.mode_vector)
+    for (const AveTimeValue& v : F->S.values) F->nrows = check_fix_column(L, v, F->nrows);
+  else
+    for (const AveTimeValue& v : F->S.values) check_fix_value(L, v);
   hipStream_t st = L.eng.stream();
   G.device(st);
   const int nv = (int)F->S.values.size();
   F->S.begin(L.eng.nsteps());
-  std::string titles[2] = {"# Time-averaged data for fix " + F->S.id, "# TimeStep"};
-  for (const AveTimeValue& v : F->S.values) titles[1] += " " + v.word;
-  fail_if(F->file.open(F->S, "ave/time", F->S.id, titles, 2));
-  F->slot = G.take(nv);
-  SF_HIP(hipMemsetAsync(G.pool + F->slot, 0, sizeof(double) * (size_t)nv, st));
+  std::string titles[3] = {"# Time-averaged data for fix " + F->S.id, "# TimeStep", ave_time_title3(F->S)};
+  if (F->S.mode_vector) titles[1] += " Number-of-rows";
+  else
+    for (const AveTimeValue& v : F->S.values) titles[1] += " " + v.word;
+  fail_if(F->file.open(F->S, "ave/time", F->S.id, titles, F->S.mode_vector ? 3 : 2));
+  if (F->S.mode_vector) {
+    SF_HIP(hipMalloc(&F->vacc, sizeof(double) * F->nacc()));
+    SF_HIP(hipMemsetAsync(F->vacc, 0, sizeof(double) * F->nacc(), st));
+  } else {
+    F->slot = G.take(nv);
+    SF_HIP(hipMemsetAsync(G.pool + F->slot, 0, sizeof(double) * (size_t)nv, st));
+  }
   G.fixes.push_back(std::move(F));
 }
 
@@ -836,14 +906,29 @@ void global_step_due(SfLammps& L, const std::vector<std::string>& also)
   std::vector<AveTimeFix*> due;
   for (auto& f : G->fixes) {
     if (f->S.catch_up(step))   // (the samples of the output that was under way are dropped)
-      SF_HIP(hipMemsetAsync(G->pool + f->slot, 0, sizeof(double) * f->S.values.size(), L.eng.stream()));
+      SF_HIP(hipMemsetAsync(f->S.mode_vector ? f->vacc : G->pool + f->slot, 0, sizeof(double) * f->nacc(), L.eng.stream()));
     if (f->S.due(step)) due.push_back(f.get());
   }
   if (due.empty() && also.empty()) return;
   if (!due.empty()) refuse_decomposed(L, "fix ave/time");
   std::vector<GlobalCompute*> want;
   std::vector<AccReq> accs;
-  for (AveTimeFix* f : due)
+  for (AveTimeFix* f : due) {
+    if (f->S.mode_vector) {   // the columns of global arrays: each array evaluated once per step (sf_nbr.hip), no host copy
+      const int nv = (int)f->S.values.size();
+      for (int j = 0; j < nv; j++) {
+        const AveTimeValue& v = f->S.values[j];
+        check_fix_column(L, v, f->nrows);
+        int ncols = 0;
+        rdf_array_rows(L, v.id, &ncols);
+        const double* src = rdf_array_device(L, v.id);
+        k_global_col_acc<<<div_up(f->nrows, kGBlock), kGBlock, 0, L.eng.stream()>>>(src + (v.index - 1), ncols, f->nrows,
+                                                                                    f->vacc + j, nv);
+        SF_HIP(hipGetLastError());
+        G->launches++;
+      }
+      continue;
+    }
     for (size_t j = 0; j < f->S.values.size(); j++) {
       const AveTimeValue& v = f->S.values[j];
       check_fix_value(L, v);
@@ -851,6 +936,7 @@ void global_step_due(SfLammps& L, const std::vector<std::string>& also)
       want.push_back(&c);
       accs.push_back({&c, (int)(v.index > 0 ? v.index - 1 : 0), G->pool ? G->pool + f->slot + j : nullptr});
     }
+  }
   for (const std::string& id : also) want.push_back(&compute_of(*G, id, "Could not find thermo custom compute ID"));
   evaluate(L, *G, want, accs);
   for (AveTimeFix* f : due)
@@ -875,6 +961,9 @@ long long sf_lammps_compute_global(void* ptr, const char* id, long long max, dou
     if (sf::atom_compute_ncols(L, id) > 0 || sf::pair_local_exists(L, id))
       sf::fail("compute %s does not calculate a global scalar or vector (sf_lammps_compute_atom and sf_lammps_get_contacts "
                "return per-atom and local values)", id);
+    if (sf::rdf_array_rows(L, id) > 0)
+      sf::fail("compute %s does not calculate a global scalar or vector (it is a global array: sf_lammps_compute_array returns "
+               "it)", id);
     sf::fail("Could not find compute ID %s", id);
   }
   if (is_vector) *is_vector = vec ? 1 : 0;
@@ -902,6 +991,19 @@ long long sf_lammps_ave_time(void* ptr, const char* id, long long max, long long
     if (!values) sf::fail("sf_lammps_ave_time: null argument");
     std::copy(F->values.begin(), F->values.end(), values);
   }
+  SF_API_END(n)
+}
+
+// rows of a mode vector fix (sf_lammps_ave_time then returns [rows][nvalues] row-major); 0: a mode scalar fix
+long long sf_lammps_ave_time_rows(void* ptr, const char* id)
+{
+  long long n = 0;
+  SF_API_BEGIN
+  if (!id) sf::fail("sf_lammps_ave_time_rows: null argument");
+  sf::GlobalSet* G = sf::set_of(*handle(ptr));
+  sf::AveTimeFix* F = G ? G->find_fix(id) : nullptr;
+  if (!F) sf::fail("Could not find fix ave/time ID %s", id);
+  n = F->S.mode_vector ? F->nrows : 0;
   SF_API_END(n)
 }
 

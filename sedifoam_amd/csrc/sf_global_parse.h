@@ -117,9 +117,10 @@ struct AveTimeValue {
   long index = 0;
 };
 
-struct AveTimeSpec : AveSchedule, AveFileSpec {   // (title3 belongs to mode vector: accepted and unused)
+struct AveTimeSpec : AveSchedule, AveFileSpec {   // (title3 belongs to mode vector: accepted and unused in mode scalar)
   std::string id, group;
   std::vector<AveTimeValue> values;
+  bool mode_vector = false;   // the values are columns c_ID[k] of global arrays with one row count (compute rdf)
   int ave = AVE_ONE;
   long window = 0;
   std::string format = " %g";
@@ -164,11 +165,11 @@ inline std::string parse_ave_time(const std::vector<std::string>& w, AveTimeSpec
     if (shared == AK_CONSUMED) continue;
     if (key == "mode") {
       if (left < 1) return illegal;
-      if (w[k + 1] == "vector") return "fix ave/time: mode vector is not supported (mode scalar is)";
-      if (w[k + 1] != "scalar") return illegal;
+      if (w[k + 1] != "scalar" && w[k + 1] != "vector") return illegal;
+      S.mode_vector = w[k + 1] == "vector";
       k += 2;
     } else if (key == "off") {
-      return "fix ave/time: off is not supported (it belongs to mode vector, which is not)";
+      return "fix ave/time: off is not supported (mode vector takes whole columns of a global array)";
     } else if (key == "format") {
       if (left < 1) return illegal;
       if (!ave_time_format_ok(w[k + 1]))
@@ -178,8 +179,23 @@ inline std::string parse_ave_time(const std::vector<std::string>& w, AveTimeSpec
     } else
       return illegal;
   }
+  if (S.mode_vector)
+    for (const AveTimeValue& v : S.values)
+      if (v.index == 0)
+        return "fix ave/time: mode vector is not supported for " + v.word + " (a global vector is not taken; c_ID[k], a column "
+               "of a global array such as compute rdf, is)";
   *out = S;
   return std::string();
+}
+
+// ---- mode vector: the text of one output ----
+
+// title3 of mode vector where none is given
+inline std::string ave_time_title3(const AveTimeSpec& S)
+{
+  std::string t = "# Row";
+  for (const AveTimeValue& v : S.values) t += " " + v.word;
+  return t;
 }
 
 // ---- thermo_style custom ... c_ID c_ID[k] ----

@@ -58,6 +58,9 @@ struct SfLammps {
   // the regions, the dynamic groups, their programs and member counts on the device (sf_region.hip); opaque like halo
   void* regions = nullptr;
   void (*regions_delete)(void*) = nullptr;
+  // the compute rdf commands, the cutoff grids and their device buffers (sf_nbr.hip); opaque like halo
+  void* nbr = nullptr;
+  void (*nbr_delete)(void*) = nullptr;
   ~SfLammps()
   {
     if (regions && regions_delete) regions_delete(regions);
@@ -70,6 +73,7 @@ struct SfLammps {
     if (chunks && chunks_delete) chunks_delete(chunks);   // (closes the files of fix ave/chunk; after the dumps, like computes)
     if (computes && computes_delete) computes_delete(computes);   // (after the dumps, whose frames read its rows)
     if (atom_computes && atom_computes_delete) atom_computes_delete(atom_computes);   // (likewise)
+    if (nbr && nbr_delete) nbr_delete(nbr);   // (after the fixes ave/time, whose samples read its arrays)
     if (halo && halo_delete) halo_delete(halo);
   }
 };

@@ -33,6 +33,7 @@
 #include "sf_contacts.h"
 #include "sf_gather_col.h"
 #include "sf_global.h"
+#include "sf_nbr.h"
 #include "sf_histo.h"
 
 // ((v - lo) * bininv stays a difference and a product, whatever the compiler would fuse around it: the bin of a value is
@@ -208,6 +209,8 @@ int check_values(const SfLammps& L, const HistoSpec& S)
     else if (atom_compute_ncols(L, v.id) > 0) kinds.push_back(HK_PERATOM);
     else if (pair_local_exists(L, v.id)) kinds.push_back(HK_LOCAL);
     else if (global_compute_nvalues(L, v.id) > 0) kinds.push_back(HK_GLOBAL);
+    else if (rdf_array_rows(L, v.id) > 0)
+      fail("Fix ave/histo compute does not calculate a global scalar or vector (c_%s is a global array, which is not binned)", v.id.c_str());
     else fail("Compute ID for fix ave/histo does not exist");
   }
   const int kind = kinds[0];

@@ -32,6 +32,7 @@
 #include "sf_dem_dispatch.h"
 #include "sf_env.h"
 #include "sf_global.h"
+#include "sf_nbr.h"
 #include "sf_global_parse.h"
 #include "sf_handles.h"
 #include "sf_thermo.h"
@@ -371,7 +372,7 @@ void check_compute_cols(const SfLammps& L, const std::vector<ComputeCol>& cols)
     bool vec = false;
     const int n = global_compute_nvalues(L, c.id, &vec);
     if (n == 0) {
-      if (atom_compute_ncols(L, c.id) > 0 || pair_local_exists(L, c.id))
+      if (atom_compute_ncols(L, c.id) > 0 || pair_local_exists(L, c.id) || rdf_array_rows(L, c.id) > 0)
         fail(c.index == 0 ? "Thermo compute does not compute scalar" : "Thermo compute does not compute vector");
       fail("Could not find thermo custom compute ID: %s", c.id.c_str());
     }

@@ -245,7 +245,50 @@ class Lammps:
         nb = check(self.L.sf_lammps_ave_time_names(self.ptr, fid, 0, None))
         buf = C.create_string_buffer(nb)
         check(self.L.sf_lammps_ave_time_names(self.ptr, fid, nb, buf))
+        rows = check(self.L.sf_lammps_ave_time_rows(self.ptr, fid))
+        if rows > 0:   # mode vector: values[nrows, nvalues]
+            val = val.reshape(rows, n // rows)
         return dict(step=step.value, values=val, names=buf.value.decode().split())
+
+    def compute_array(self, cid):
+        """the global array of `compute cid group rdf Nbin [itype jtype ...] cutoff Rc` on the positions as they stand:
+        float64 [Nbin, 1 + 2 npairs] -- the bin centre, then g(r) and the running coordination number of each pair.  What a
+        fix ave/time mode vector sample taken at this moment holds.  Passive: the run goes on with the same bits"""
+        cid = str(cid).encode()
+        nc = C.c_int()
+        n = check(self.L.sf_lammps_compute_array(self.ptr, cid, 0, None, C.byref(nc)))
+        val = np.zeros(n)
+        m = check(self.L.sf_lammps_compute_array(self.ptr, cid, n, _p(val), C.byref(nc)))
+        assert m == n
+        return val.reshape(n // nc.value, nc.value)
+
+    def rdf_counts(self, cid):
+        """the raw counts of compute rdf `cid`: dict(counts int64 [npairs, Nbin] ordered pairs per bin, icount, jcount,
+        duplicates int64 [npairs])"""
+        cid = str(cid).encode()
+        npairs = C.c_int()
+        n = check(self.L.sf_lammps_rdf_counts(self.ptr, cid, 0, None, None, C.byref(npairs)))
+        counts = np.zeros(n, np.int64)
+        per = np.zeros(3 * npairs.value, np.int64)
+        ll = C.POINTER(C.c_longlong)
+        m = check(self.L.sf_lammps_rdf_counts(self.ptr, cid, n, counts.ctypes.data_as(ll), per.ctypes.data_as(ll), C.byref(npairs)))
+        assert m == n
+        per = per.reshape(npairs.value, 3)
+        return dict(counts=counts.reshape(npairs.value, n // npairs.value), icount=per[:, 0].copy(), jcount=per[:, 1].copy(),
+                    duplicates=per[:, 2].copy())
+
+    def nbr_launches(self):
+        """dict(grid_builds, launches, host_copies): cutoff grids built, kernel launches made and device-to-host copies made
+        for compute rdf and coord/atom so far"""
+        g = C.c_longlong(); n = C.c_longlong(); h = C.c_longlong()
+        check(self.L.sf_lammps_nbr_launches(self.ptr, C.byref(g), C.byref(n), C.byref(h)))
+        return dict(grid_builds=g.value, launches=n.value, host_copies=h.value)
+
+    def nbr_cost(self, cid):
+        """GPU ms of (one fresh grid build, one walk) of compute rdf or coord/atom `cid` now"""
+        g = C.c_double(); w = C.c_double()
+        check(self.L.sf_lammps_nbr_cost(self.ptr, str(cid).encode(), C.byref(g), C.byref(w)))
+        return g.value, w.value
 
     def global_launches(self):
         """dict(launches, host_copies): kernel launches made for global computes and fix ave/time so far, and the
