@@ -44,11 +44,6 @@ struct AveFixState {
   long long out_step = -1;
 };
 
-inline void fail_if(const std::string& err)
-{
-  if (!err.empty()) fail("%s", err.c_str());
-}
-
 template <class F>
 F* ave_find(const std::vector<std::unique_ptr<F>>& fixes, const std::string& id)
 {

@@ -33,9 +33,7 @@
 #include "sf_chunk.h"
 #include "sf_chunk_parse.h"
 #include "sf_compute_atom.h"
-#include "sf_contacts.h"
-#include "sf_global.h"
-#include "sf_nbr.h"
+#include "sf_compute_ids.h"
 
 namespace sf {
 namespace {
@@ -184,29 +182,6 @@ __global__ __launch_bounds__(256) void k_chunk_fold(const double* partial, long 
 
 // ---- host side ----
 
-struct Grown {   // device scratch, grown geometrically (no allocation per sample once it has grown)
-  void* p = nullptr;
-  size_t n = 0;
-  void* get(size_t need, hipStream_t s)
-  {
-    if (need > n) {
-      if (p) {
-        SF_HIP(hipStreamSynchronize(s));
-        SF_HIP(hipFree(p));
-      }
-      n = need + need / 4 + 4096;
-      SF_HIP(hipMalloc(&p, n));
-    }
-    return p;
-  }
-  template <class T>
-  T* as() const { return static_cast<T*>(p); }
-  ~Grown()
-  {
-    if (p) (void)hipFree(p);
-  }
-};
-
 struct RawTmp {   // the scratch of the sort and scan wrappers of sf_sort.hip, which grow it themselves
   void* p = nullptr;
   size_t n = 0;
@@ -221,18 +196,16 @@ struct ChunkCompute {
   int groupbit = 1;
   ChunkBins B;
   int keybits = 1;
-  Grown val, key_in, idx_in, key_out, idx_out, start, ntile, tileoff;
+  DeviceScratch val, key_in, idx_in, key_out, idx_out, start, ntile, tileoff;
   RawTmp sort_tmp, scan_tmp;
-  // what the assignment / the grouping was made at (-1: nothing)
-  long long step = -1, nbuilds = -1, gstep = -1, gnbuilds = -1;
-  int nlocal = -1, gnlocal = -1;
+  StateStamp assigned, grouped;   // what the assignment / the grouping was made at
 };
 
 struct AveFix : AveFixState {
   AveSpec S;
   int groupbit = 1;
   int nchunk = 0, ncol = 1;
-  Grown partial, acc, cost_acc;
+  DeviceScratch partial, acc, cost_acc;
   std::vector<double> h_acc;
   // ave running: the sums of norm all (device layout) and the sums of the per-output results, over noutputs outputs
   std::vector<double> run_acc, run_res;
@@ -253,21 +226,8 @@ struct ChunkSet {
   AveFix* find_fix(const std::string& id) const { return ave_find(fixes, id); }
 };
 
-ChunkSet* set_of(const SfLammps& L) { return static_cast<ChunkSet*>(L.chunks); }
-ChunkSet& ensure_set(SfLammps& L)
-{
-  if (!L.chunks) {
-    L.chunks = new ChunkSet();
-    L.chunks_delete = [](void* p) { delete static_cast<ChunkSet*>(p); };
-  }
-  return *set_of(L);
-}
-
-bool assigned_now(const SfLammps& L, const ChunkCompute& c)
-{
-  const DemEngine& e = L.eng;
-  return c.step == e.nsteps() && c.nbuilds == e.nbuilds() && c.nlocal == e.nlocal();
-}
+ChunkSet* set_of(const SfLammps& L) { return L.chunks.get<ChunkSet>(); }
+ChunkSet& ensure_set(SfLammps& L) { return L.chunks.ensure<ChunkSet>(); }
 
 void assign(SfLammps& L, ChunkSet& T, ChunkCompute& c)
 {
@@ -284,10 +244,8 @@ void assign(SfLammps& L, ChunkSet& T, ChunkCompute& c)
     SF_HIP(hipGetLastError());
     T.launches++;
   }
-  c.step = e.nsteps();
-  c.nbuilds = e.nbuilds();
-  c.nlocal = n;
-  c.gstep = -1;
+  c.assigned.set(e);
+  c.grouped.clear();
 }
 
 // sort + bounds + tiles + scan of the assignment of this step (made first when it is stale)
@@ -313,14 +271,11 @@ void group_sorted(SfLammps& L, ChunkSet& T, ChunkCompute& c)
 
 void group(SfLammps& L, ChunkSet& T, ChunkCompute& c)
 {
-  if (!assigned_now(L, c)) assign(L, T, c);
+  if (!c.assigned.is_now(L.eng)) assign(L, T, c);
   else refuse_decomposed(L, "compute chunk/atom");
-  const DemEngine& e = L.eng;
-  if (c.gstep == e.nsteps() && c.gnbuilds == e.nbuilds() && c.gnlocal == e.nlocal()) return;
+  if (c.grouped.is_now(L.eng)) return;
   group_sorted(L, T, c);
-  c.gstep = e.nsteps();
-  c.gnbuilds = e.nbuilds();
-  c.gnlocal = e.nlocal();
+  c.grouped.set(L.eng);
 }
 
 Src src_of(int source)
@@ -343,13 +298,7 @@ bool per_atom_value(int source) { return source != AS_DENSITY_NUMBER && source !
 // the column of a c_ value: checked at the fix line and again at every sample (the compute may have been redefined)
 void check_compute_value(const SfLammps& L, const AveValue& v)
 {
-  const int nc = atom_compute_ncols(L, v.id);
-  if (nc == 0 && (pair_local_exists(L, v.id) || global_compute_nvalues(L, v.id) > 0 || rdf_array_rows(L, v.id) > 0))
-    fail("Fix ave/chunk compute does not calculate per-atom values");
-  if (nc == 0) fail("Compute ID for fix ave/chunk does not exist");
-  if (v.index == 0 && nc != 1) fail("Fix ave/chunk compute does not calculate a per-atom vector");
-  if (v.index > 0 && nc == 1) fail("Fix ave/chunk compute does not calculate a per-atom array");
-  if (v.index > nc) fail("Fix ave/chunk compute vector is accessed out-of-range");
+  fail_if(check_ave_chunk_value(compute_shape(L, v.id), v.index));
 }
 
 // the sums of one sample of fix F, added into acc (the fix's accumulator, or the scratch of the cost measurement)
@@ -557,22 +506,20 @@ void chunk_compute_define(SfLammps& L, const std::vector<std::string>& w)
   ensure_set(L).computes.push_back(std::move(c));
 }
 
-bool chunk_compute_exists(const SfLammps& L, const std::string& id)
+bool chunk_compute_shape(const SfLammps& L, const std::string& id, ComputeShape* s)
 {
   ChunkSet* T = set_of(L);
-  return T && T->find(id);
+  if (!T || !T->find(id)) return false;
+  *s = ComputeShape();
+  s->kind = CK_PERATOM;
+  s->n = 1;
+  s->chunk = true;
+  return true;
 }
 
 void chunk_compute_remove(SfLammps& L, const std::string& id)
 {
-  ChunkSet* T = set_of(L);
-  if (!T) return;
-  for (size_t k = 0; k < T->computes.size(); k++)
-    if (T->computes[k]->id == id) {
-      SF_HIP(hipStreamSynchronize(L.eng.stream()));   // (a frame queued on the stream may still read its buffer)
-      T->computes.erase(T->computes.begin() + k);
-      return;
-    }
+  if (ChunkSet* T = set_of(L)) compute_take(L, T->computes, id);   // (a frame queued on the stream may still read its buffer)
 }
 
 const double* chunk_compute_values(SfLammps& L, const std::string& id)
@@ -580,7 +527,7 @@ const double* chunk_compute_values(SfLammps& L, const std::string& id)
   ChunkSet* T = set_of(L);
   ChunkCompute* c = T ? T->find(id) : nullptr;
   if (!c) fail("Could not find compute ID %s", id.c_str());
-  if (!assigned_now(L, *c)) assign(L, *T, *c);
+  if (!c->assigned.is_now(L.eng)) assign(L, *T, *c);
   else refuse_decomposed(L, "compute chunk/atom");
   return c->val.as<double>();
 }
@@ -588,7 +535,10 @@ const double* chunk_compute_values(SfLammps& L, const std::string& id)
 void chunk_invalidate(SfLammps& L)
 {
   if (ChunkSet* T = set_of(L))
-    for (auto& c : T->computes) c->step = c->gstep = -1;
+    for (auto& c : T->computes) {
+      c->assigned.clear();
+      c->grouped.clear();
+    }
 }
 
 // ---- the fix ----
@@ -605,13 +555,8 @@ void ave_chunk_fix_command(SfLammps& L, const std::string& line)
   ChunkSet& T = ensure_set(L);
   if (ave_fix_exists(L, F->S.id))
     fail("fix ave/chunk %s: this fix ID is in use (unfix it first)", F->S.id.c_str());
+  fail_if(check_ave_chunk_id(compute_shape(L, F->S.chunk)));
   ChunkCompute* c = T.find(F->S.chunk);
-  if (!c) {
-    if (atom_compute_ncols(L, F->S.chunk) > 0 || pair_local_exists(L, F->S.chunk) || global_compute_nvalues(L, F->S.chunk) > 0 ||
-        rdf_array_rows(L, F->S.chunk) > 0)
-      fail("Fix ave/chunk does not use chunk/atom compute");
-    fail("Chunk/atom compute does not exist for fix ave/chunk");
-  }
   for (const AveValue& v : F->S.values)
     if (v.source == AS_COMPUTE) check_compute_value(L, v);
   F->nchunk = c->B.nchunk;
@@ -731,9 +676,7 @@ int sf_lammps_ave_chunk_cost(void* ptr, const char* id, double* out3)
   sf::assign(L, *T, c);
   SF_HIP(hipEventRecord(ev[1], st));
   sf::group_sorted(L, *T, c);
-  c.gstep = L.eng.nsteps();
-  c.gnbuilds = L.eng.nbuilds();
-  c.gnlocal = L.eng.nlocal();
+  c.grouped.set(L.eng);
   SF_HIP(hipEventRecord(ev[2], st));
   sf::launch_sums(L, *T, *F, c, scratch);
   SF_HIP(hipEventRecord(ev[3], st));

@@ -1,8 +1,8 @@
 // sf_compute_atom.h -- the per-atom computes `compute ID group stress/atom | contact/atom | ke/atom | erotate/sphere/atom |
 // property/atom` (sf_compute_atom.hip): one value (stress/atom: six; property/atom: one per attribute) per owned atom, evaluated on the GPU from the state at the moment of
 // the output, behind the `c_ID` / `c_ID[k]` columns of `dump custom` (sf_dump.hip) and sf_lammps_compute_atom.  They share
-// the ID space of `compute pair/local`: compute_command (sf_contacts.hip) owns `compute` / `uncompute` and hands these
-// styles over.
+// the ID space of the other computes: sf_compute_ids.h owns `compute` / `uncompute`, and these styles (chunk/atom of
+// sf_chunk.hip among them, forwarded) plug in there as atom_compute_kind().
 #pragma once
 #include <string>
 #include <vector>
@@ -12,19 +12,10 @@
 namespace sf {
 struct SfLammps;
 
-// is `style` one of the per-atom styles of this file?
-bool atom_compute_style(const std::string& style);
-// `compute ID group STYLE ...` of such a style (the caller has checked that the ID is new)
-void atom_compute_define(SfLammps& L, const std::vector<std::string>& w);
-// columns of compute `id` (1, 6 for stress/atom, the attributes of property/atom); 0: no per-atom compute has this ID
-int atom_compute_ncols(const SfLammps& L, const std::string& id);
-void atom_compute_remove(SfLammps& L, const std::string& id);
 // The values of compute `id` on the state as it stands, field-major on the device: column c of atom index i at
 // [c * nlocal + i]; atoms outside the compute's group hold 0.  Evaluated once per step however many dumps and queries
 // ask: the buffer is kept with the step (and the rebuild and atom counts) it was made at, on the engine's stream.
 const double* atom_compute_values(SfLammps& L, const std::string& id, int* ncols);
-// the state changed at an unchanged step (a script command, atoms created or deleted): evaluate again when asked next
-void atom_compute_invalidate(SfLammps& L);
 long long atom_compute_launches(const SfLammps& L);
 // GPU time from HIP events of one fresh evaluation of `id` (tools/compute_atom_cost.py)
 double atom_compute_cost(SfLammps& L, const std::string& id);

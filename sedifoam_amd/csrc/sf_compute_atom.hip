@@ -37,11 +37,11 @@
 #include "sf_atom_terms.h"
 #include "sf_chunk.h"
 #include "sf_compute_atom.h"
+#include "sf_compute_ids.h"
 #include "sf_compute_parse.h"
 #include "sf_dem_dispatch.h"
 #include "sf_displace.h"
 #include "sf_displace_parse.h"
-#include "sf_global.h"
 #include "sf_global_parse.h"
 #include "sf_handles.h"
 #include "sf_nbr.h"
@@ -261,27 +261,6 @@ constexpr int kNumKinds = 7;
 const char* const kStyleName[kNumKinds] = {"stress/atom", "contact/atom", "ke/atom", "erotate/sphere/atom", "property/atom",
                                            "displace/atom", "coord/atom"};
 
-struct Grown {   // device scratch, grown geometrically (no allocation per frame once it has grown)
-  void* p = nullptr;
-  size_t n = 0;
-  void* get(size_t need, hipStream_t s)
-  {
-    if (need > n) {
-      if (p) {
-        SF_HIP(hipStreamSynchronize(s));
-        SF_HIP(hipFree(p));
-      }
-      n = need + need / 4 + 4096;
-      SF_HIP(hipMalloc(&p, n));
-    }
-    return p;
-  }
-  ~Grown()
-  {
-    if (p) (void)hipFree(p);
-  }
-};
-
 struct AtomCompute {
   std::string id;
   Kind kind = K_KE;
@@ -290,10 +269,8 @@ struct AtomCompute {
   std::vector<int> attrs;   // K_PROPERTY
   RefTable ref;             // K_DISPLACE: the reference positions, by tag
   CoordSpec coord;          // K_COORD: the cutoff and the type ranges
-  Grown val;
-  // what the buffer was made at (-1: nothing)
-  long long step = -1, nbuilds = -1;
-  int nlocal = -1;
+  DeviceScratch val;
+  StateStamp made;   // what the buffer was made at
   int ncols() const
   {
     if (kind == K_COORD) return (int)coord.ranges.size();
@@ -322,15 +299,8 @@ struct AtomSet {
 
 std::string AtomCompute::who() const { return std::string("compute ") + kStyleName[kind]; }
 
-AtomSet* set_of(const SfLammps& L) { return static_cast<AtomSet*>(L.atom_computes); }
-AtomSet& ensure_set(SfLammps& L)
-{
-  if (!L.atom_computes) {
-    L.atom_computes = new AtomSet();
-    L.atom_computes_delete = [](void* p) { delete static_cast<AtomSet*>(p); };
-  }
-  return *set_of(L);
-}
+AtomSet* set_of(const SfLammps& L) { return L.atom_computes.get<AtomSet>(); }
+AtomSet& ensure_set(SfLammps& L) { return L.atom_computes.ensure<AtomSet>(); }
 
 // what an evaluation needs of the engine as it is now (checked at the compute line and at every evaluation: the pair
 // style and the fixes may have changed since)
@@ -399,14 +369,12 @@ void evaluate(SfLammps& L, AtomSet& T, AtomCompute& c)
     SF_HIP(hipGetLastError());
     T.launches++;
   }
-  c.step = e.nsteps();
-  c.nbuilds = e.nbuilds();
-  c.nlocal = n;
+  c.made.set(e);
 }
 
-}  // namespace
+// ---- the kind (sf_compute_ids.h) ----
 
-bool atom_compute_style(const std::string& style)
+bool is_style(const std::string& style)
 {
   if (style == "chunk/atom") return true;   // (the fifth per-atom style: sf_chunk.hip holds it, the functions below forward)
   for (const char* s : kStyleName)
@@ -414,7 +382,7 @@ bool atom_compute_style(const std::string& style)
   return false;
 }
 
-void atom_compute_define(SfLammps& L, const std::vector<std::string>& w)
+void define(SfLammps& L, const std::vector<std::string>& w)
 {
   if (w[3] == "chunk/atom") {
     chunk_compute_define(L, w);
@@ -447,53 +415,50 @@ void atom_compute_define(SfLammps& L, const std::vector<std::string>& w)
   ensure_set(L).computes.push_back(std::move(c));
 }
 
-int atom_compute_ncols(const SfLammps& L, const std::string& id)
+bool shape(const SfLammps& L, const std::string& id, ComputeShape* s)
 {
   AtomSet* T = set_of(L);
   const AtomCompute* c = T ? T->find(id) : nullptr;
-  if (!c && chunk_compute_exists(L, id)) return 1;
-  return c ? c->ncols() : 0;
+  if (!c) return chunk_compute_shape(L, id, s);
+  *s = ComputeShape();
+  s->kind = CK_PERATOM;
+  s->n = c->ncols();
+  return true;
 }
 
-void atom_compute_remove(SfLammps& L, const std::string& id)
+void remove(SfLammps& L, const std::string& id)
 {
   chunk_compute_remove(L, id);
-  AtomSet* T = set_of(L);
-  if (!T) return;
-  for (size_t k = 0; k < T->computes.size(); k++)
-    if (T->computes[k]->id == id) {
-      SF_HIP(hipStreamSynchronize(L.eng.stream()));   // (a frame queued on the stream may still read its buffer)
-      T->computes.erase(T->computes.begin() + k);
-      return;
-    }
+  if (AtomSet* T = set_of(L)) compute_take(L, T->computes, id);   // (a frame queued on the stream may still read its buffer)
+}
+
+void invalidate(SfLammps& L)
+{
+  if (AtomSet* T = set_of(L))
+    for (auto& c : T->computes) c->made.clear();
+}
+
+}  // namespace
+
+const ComputeKindOps& atom_compute_kind()
+{
+  static const ComputeKindOps kind = {is_style, define, remove, shape, invalidate};
+  return kind;
 }
 
 const double* atom_compute_values(SfLammps& L, const std::string& id, int* ncols)
 {
   AtomSet* T = set_of(L);
   AtomCompute* c = T ? T->find(id) : nullptr;
-  if (!c && chunk_compute_exists(L, id)) {
-    if (ncols) *ncols = 1;
+  if (!c) {
+    fail_if(check_get_atom(compute_shape(L, id), id));
+    if (ncols) *ncols = 1;   // (a per-atom compute that is not held here: chunk/atom)
     return chunk_compute_values(L, id);
   }
-  if (!c && global_compute_nvalues(L, id) > 0) fail("compute %s does not calculate per-atom values (it is a global compute)", id.c_str());
-  if (!c && rdf_array_rows(L, id) > 0)
-    fail("compute %s does not calculate per-atom values (it is a global array: sf_lammps_compute_array returns it)", id.c_str());
-  if (!c) fail("Could not find compute ID %s", id.c_str());
-  const DemEngine& e = L.eng;
-  if (c->step != e.nsteps() || c->nbuilds != e.nbuilds() || c->nlocal != e.nlocal()) evaluate(L, *T, *c);
+  if (!c->made.is_now(L.eng)) evaluate(L, *T, *c);
   else refuse_unsupported(L, c->kind);
   if (ncols) *ncols = c->ncols();
   return static_cast<const double*>(c->val.p);
-}
-
-void atom_compute_invalidate(SfLammps& L)
-{
-  chunk_invalidate(L);
-  global_invalidate(L);
-  nbr_invalidate(L);
-  if (AtomSet* T = set_of(L))
-    for (auto& c : T->computes) c->step = -1;
 }
 
 bool atom_compute_coord_spec(const SfLammps& L, const std::string& id, int* groupbit, double* rc, std::vector<TypeRange>* ranges)
@@ -531,10 +496,9 @@ long long atom_compute_launches(const SfLammps& L)
 
 double atom_compute_cost(SfLammps& L, const std::string& id)
 {
+  fail_if(check_atom_cost(compute_shape(L, id), id));
   AtomSet* T = set_of(L);
-  AtomCompute* c = T ? T->find(id) : nullptr;
-  if (!c && chunk_compute_exists(L, id)) fail("compute %s is a chunk/atom compute: sf_lammps_ave_chunk_cost times its pass", id.c_str());
-  if (!c) fail("Could not find compute ID %s", id.c_str());
+  AtomCompute* c = T->find(id);
   hipStream_t st = L.eng.stream();
   c->val.get(sizeof(double) * (size_t)c->ncols() * (size_t)std::max(L.eng.nlocal(), 1), st);   // (not in the time)
   return stream_ms(st, [&] { evaluate(L, *T, *c); });

@@ -1,6 +1,7 @@
-// sf_contacts.h -- `compute ID group pair/local v...` (the reference's name: gran/local), `uncompute ID` and the rows behind
+// sf_contacts.h -- `compute ID group pair/local v...` (the reference's name: gran/local) and the rows behind
 // `dump ID group local N file col...` and sf_lammps_get_contacts (sf_contacts.hip): one row per touching pair, evaluated on
-// the GPU from the state at the moment of the output.
+// the GPU from the state at the moment of the output.  The ID space, `compute` and `uncompute` are sf_compute_ids.h's; this
+// kind plugs in there as pair_local_kind().
 #pragma once
 #include <string>
 #include <vector>
@@ -32,11 +33,7 @@ struct ContactCols {   // the columns of a text line: ContactValue or kContactIn
   unsigned char c[kContactMaxCols];
 };
 
-// `compute` / `uncompute`: true when the word was one of the two
-bool compute_command(SfLammps& L, const std::vector<std::string>& w);
-// is `id` a compute pair/local?
-bool pair_local_exists(const SfLammps& L, const std::string& id);
-// the values and the group of compute `id` (fails with LAMMPS' wording when there is none)
+// the values and the group of compute pair/local `id` (fails with LAMMPS' wording when there is none)
 void compute_lookup(const SfLammps& L, const std::string& id, std::vector<unsigned char>* values, int* groupbit);
 // count + scan + rows on the engine's stream; synchronises it once (the row count).  ms != nullptr: the GPU time of the
 // three launches from HIP events (the wait for the count lies between two pairs of events and is not in it)

@@ -33,15 +33,10 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/sedifoam_amd.h"
-#include "sf_chunk.h"
-#include "sf_compute_atom.h"
+#include "sf_compute_ids.h"
 #include "sf_contacts.h"
 #include "sf_dem_dispatch.h"
 #include "sf_dump_fmt.h"
-#include "sf_global.h"
-#include "sf_nbr.h"
-#include "sf_ave_fix.h"
-#include "sf_thermo.h"
 
 namespace sf {
 namespace {
@@ -233,30 +228,9 @@ struct Compute {
   std::vector<unsigned char> values;
 };
 
-struct Grown {   // device scratch, grown geometrically (a frame comes every N steps: no allocation per frame)
-  void* p = nullptr;
-  size_t n = 0;
-  void* get(size_t need, hipStream_t s)
-  {
-    if (need > n) {
-      if (p) {
-        SF_HIP(hipStreamSynchronize(s));
-        SF_HIP(hipFree(p));
-      }
-      n = need + need / 4 + 4096;
-      SF_HIP(hipMalloc(&p, n));
-    }
-    return p;
-  }
-  ~Grown()
-  {
-    if (p) (void)hipFree(p);
-  }
-};
-
 struct ContactSet {
   std::vector<Compute> computes;
-  Grown cnt, off, tags, vals;
+  DeviceScratch cnt, off, tags, vals;   // (a frame comes every N steps: no allocation per frame)
   void* scan_tmp = nullptr;
   size_t scan_bytes = 0;
   int* h_total = nullptr;   // pinned
@@ -277,15 +251,8 @@ struct ContactSet {
   }
 };
 
-ContactSet* set_of(const SfLammps& L) { return static_cast<ContactSet*>(L.computes); }
-ContactSet& ensure_set(SfLammps& L)
-{
-  if (!L.computes) {
-    L.computes = new ContactSet();
-    L.computes_delete = [](void* p) { delete static_cast<ContactSet*>(p); };
-  }
-  return *set_of(L);
-}
+ContactSet* set_of(const SfLammps& L) { return L.computes.get<ContactSet>(); }
+ContactSet& ensure_set(SfLammps& L) { return L.computes.ensure<ContactSet>(); }
 
 // what an evaluation needs of the engine as it is now (the compute command checks it, and every evaluation again: the
 // pair style and the fixes may have changed since)
@@ -310,70 +277,16 @@ bool DemEngine::contact_view(DemPtrs* P, StepParams* S) const
   return have_list_;
 }
 
-// compute ID group-ID pair/local v1 v2 ...  |  compute ID group-ID gran/local ...  |  uncompute ID
-bool compute_command(SfLammps& L, const std::vector<std::string>& w)
+// ---- the kind (sf_compute_ids.h) ----
+namespace {
+bool is_style(const std::string& style) { return style == "pair/local" || style == "gran/local"; }
+
+// compute ID group-ID pair/local v1 v2 ...  |  compute ID group-ID gran/local ...
+void define(SfLammps& L, const std::vector<std::string>& w)
 {
-  if (w[0] == "uncompute") {
-    if (w.size() != 2) fail("Illegal uncompute command");
-    ContactSet* S = set_of(L);
-    Compute* c = S ? S->find(w[1]) : nullptr;
-    const bool per_atom = !c && atom_compute_ncols(L, w[1]) > 0;   // (one ID space: sf_compute_atom.hip holds the others)
-    const bool global = !c && !per_atom && global_compute_nvalues(L, w[1]) > 0;   // (sf_global.hip holds those)
-    const bool array = !c && !per_atom && !global && rdf_array_rows(L, w[1]) > 0;   // (sf_nbr.hip holds compute rdf)
-    if (!c && !per_atom && !global && !array) fail("Could not find compute ID to delete");   // [3P] Modify::delete_compute
-    if (reduce_uses_compute(L, w[1])) fail("uncompute %s: a compute reduce still uses this compute (uncompute it first)", w[1].c_str());
-    if (const char* who = ave_fix_uses_compute(L, w[1]))
-      fail("uncompute %s: a %s still uses this compute (unfix it first)", w[1].c_str(), who);
-    if (array) {
-      rdf_compute_remove(L, w[1]);
-      return true;
-    }
-    if (global) {
-      if (thermo_uses_compute(L, w[1]))
-        fail("uncompute %s: thermo_style custom still names this compute (give another thermo_style first)", w[1].c_str());
-      global_compute_remove(L, w[1]);
-      return true;
-    }
-    if (dump_uses_compute(L, w[1]))
-      fail("uncompute %s: a dump %s still uses this compute (undump it first)", w[1].c_str(), per_atom ? "custom" : "local");
-    if (per_atom) {
-      atom_compute_remove(L, w[1]);
-      return true;
-    }
-    S->computes.erase(S->computes.begin() + (c - S->computes.data()));
-    return true;
-  }
-  if (w[0] != "compute") return false;
-  if (w.size() < 4) fail("Illegal compute command");
-  const std::string& style = w[3];
-  if (style == "cohe/local")
-    fail("compute cohe/local is not built (fix cohesive is a fix and has no single(); the reference's own code behind it "
-         "never terminates)");
-  const bool per_atom = atom_compute_style(style), global = global_compute_style(style);
-  const bool array = rdf_compute_style(style);
-  if (style != "pair/local" && style != "gran/local" && !per_atom && !global && !array)
-    fail("Invalid compute style %s (this engine has compute pair/local, also under the name gran/local, the per-atom "
-         "computes stress/atom, contact/atom, ke/atom, erotate/sphere/atom, property/atom and chunk/atom, and the global "
-         "computes reduce, ke and erotate/sphere; on unwrapped coordinates the per-atom compute displace/atom and the global "
-         "compute com; on a grid of the user's cutoff the global array rdf and the per-atom compute coord/atom)", style.c_str());
   Compute c;
   c.id = w[1];
   c.groupbit = L.eng.group_bit(w[2]);
-  if ((set_of(L) && set_of(L)->find(c.id)) || atom_compute_ncols(L, c.id) > 0 || global_compute_nvalues(L, c.id) > 0 ||
-      rdf_array_rows(L, c.id) > 0)
-    fail("Reuse of compute ID");
-  if (array) {
-    rdf_compute_define(L, w);   // (sf_nbr.hip)
-    return true;
-  }
-  if (global) {
-    global_compute_define(L, w);   // (sf_global.hip)
-    return true;
-  }
-  if (per_atom) {
-    atom_compute_define(L, w);   // (sf_compute_atom.hip)
-    return true;
-  }
   if (w.size() < 5) fail("Illegal compute pair/local command");
   refuse_unsupported(L, "compute pair/local");
   for (size_t k = 4; k < w.size(); k++) {
@@ -389,25 +302,40 @@ bool compute_command(SfLammps& L, const std::vector<std::string>& w)
     c.values.push_back((unsigned char)v);
   }
   ensure_set(L).computes.push_back(std::move(c));
+}
+
+// (no wait for the stream, unlike the other kinds: a compute pair/local holds no device buffer of its own -- the rows are
+// the set's scratch, which stays)
+void remove(SfLammps& L, const std::string& id)
+{
+  ContactSet* S = set_of(L);
+  if (Compute* c = S ? S->find(id) : nullptr) S->computes.erase(S->computes.begin() + (c - S->computes.data()));
+}
+
+bool shape(const SfLammps& L, const std::string& id, ComputeShape* s)
+{
+  ContactSet* S = set_of(L);
+  const Compute* c = S ? S->find(id) : nullptr;
+  if (!c) return false;
+  *s = ComputeShape();
+  s->kind = CK_LOCAL;
+  s->n = (int)c->values.size();
   return true;
 }
 
-bool pair_local_exists(const SfLammps& L, const std::string& id)
+void invalidate(SfLammps&) {}   // (the rows are made anew at every request)
+}  // namespace
+
+const ComputeKindOps& pair_local_kind()
 {
-  ContactSet* S = set_of(L);
-  return S && S->find(id);
+  static const ComputeKindOps kind = {is_style, define, remove, shape, invalidate};
+  return kind;
 }
 
 void compute_lookup(const SfLammps& L, const std::string& id, std::vector<unsigned char>* values, int* groupbit)
 {
   ContactSet* S = set_of(L);
   const Compute* c = S ? S->find(id) : nullptr;
-  if (!c && atom_compute_ncols(L, id) > 0)   // [3P] DumpLocal::parse_fields
-    fail("Dump local compute does not compute local info: %s is a per-atom compute (dump custom prints it)", id.c_str());
-  if (!c && global_compute_nvalues(L, id) > 0)
-    fail("Dump local compute does not compute local info: %s is a global compute (fix ave/time and thermo print it)", id.c_str());
-  if (!c && rdf_array_rows(L, id) > 0)
-    fail("Dump local compute does not compute local info: %s is a global array (fix ave/time mode vector prints it)", id.c_str());
   if (!c) fail("Could not find dump local compute ID %s", id.c_str());
   if (values) *values = c->values;
   if (groupbit) *groupbit = c->groupbit;

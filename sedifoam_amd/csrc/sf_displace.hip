@@ -70,14 +70,7 @@ struct Staging {   // device scratch of this file, grown and kept
   }
 };
 
-Staging& staging_of(SfLammps& L)
-{
-  if (!L.displace) {
-    L.displace = new Staging();
-    L.displace_delete = [](void* p) { delete static_cast<Staging*>(p); };
-  }
-  return *static_cast<Staging*>(L.displace);
-}
+Staging& staging_of(SfLammps& L) { return L.displace.ensure<Staging>(); }
 
 }  // namespace
 

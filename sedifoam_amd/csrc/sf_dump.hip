@@ -36,13 +36,11 @@
 #include "../../include/sedifoam_amd.h"
 #include "sf_common.h"
 #include "sf_compute_atom.h"
+#include "sf_compute_ids.h"
 #include "sf_compute_parse.h"
 #include "sf_contacts.h"
 #include "sf_dump.h"
 #include "sf_dump_fmt.h"
-#include "sf_global.h"
-#include "sf_nbr.h"
-#include "sf_handles.h"
 
 namespace sf {
 namespace {
@@ -155,30 +153,8 @@ __global__ __launch_bounds__(256) void k_dump_compact(const char* slots, int str
   }
 }
 
-// device scratch of the format + compact pipeline, grown geometrically
-struct DevBuf {
-  void* p = nullptr;
-  size_t n = 0;
-  void* get(size_t need, hipStream_t s)
-  {
-    if (need > n) {
-      if (p) {
-        SF_HIP(hipStreamSynchronize(s));
-        SF_HIP(hipFree(p));
-      }
-      n = need + need / 4 + 4096;
-      SF_HIP(hipMalloc(&p, n));
-    }
-    return p;
-  }
-  ~DevBuf()
-  {
-    if (p) (void)hipFree(p);
-  }
-};
-
 struct Pipeline {
-  DevBuf slots, len, off, out, scan, small;
+  DeviceScratch slots, len, off, out, scan, small;   // of the format + compact pipeline
   // format nslots slots of `stride` bytes (the caller's kernel `fill` writes them and their lengths into len), then
   // compact; returns the byte count (synchronises the stream once, after the scan) -- the bytes are in out.p.
   // ev: four events around the launches in front of and behind that wait (tools/contact_cost.py)
@@ -348,16 +324,8 @@ struct DumpSet {
   }
 };
 
-DumpSet* set_of(const SfLammps& L) { return static_cast<DumpSet*>(L.dumps); }
-
-DumpSet& ensure_set(SfLammps& L)
-{
-  if (!L.dumps) {
-    L.dumps = new DumpSet();
-    L.dumps_delete = [](void* p) { delete static_cast<DumpSet*>(p); };
-  }
-  return *set_of(L);
-}
+DumpSet* set_of(const SfLammps& L) { return L.dumps.get<DumpSet>(); }
+DumpSet& ensure_set(SfLammps& L) { return L.dumps.ensure<DumpSet>(); }
 
 std::string replace_all(std::string s, char c, const std::string& by)
 {
@@ -482,7 +450,7 @@ void format_values(const double* values, long long nvalues, const int* ints, lon
     hipStream_t s;
     ~StreamGuard() { (void)hipStreamDestroy(s); }
   } sg{s};
-  DevBuf din;
+  DeviceScratch din;
   char* base = static_cast<char*>(din.get(sizeof(double) * nvalues + sizeof(int) * nints + 16, s));
   double* d_val = reinterpret_cast<double*>(base);
   int* d_int = reinterpret_cast<int*>(base + sizeof(double) * nvalues);
@@ -548,18 +516,15 @@ void dump_command(SfLammps& L, const std::vector<std::string>& w)
             sf::fail("Invalid attribute %s in dump local command", w[k].c_str());
           id.resize(br);
         }
-        if (d->compute.empty()) {
-          compute_lookup(L, id, &values, nullptr);   // "Could not find dump local compute ID"
-          d->compute = id;
-        } else if (id != d->compute)
+        if (!d->compute.empty() && id != d->compute)
           sf::fail("dump local: every c_ column must name the same compute (%s and %s): the rows of two computes are "
                    "not the same rows", d->compute.c_str(), id.c_str());
-        if (br == std::string::npos) {
-          if (values.size() != 1) sf::fail("Dump local compute does not compute local vector: %s", w[k].c_str());
-          idx = 1;
-        } else if (idx > (long)values.size())
-          sf::fail("Dump local compute vector is accessed out-of-range: %s", w[k].c_str());
-        c = values[idx - 1];
+        fail_if(check_dump_local(compute_shape(L, id), idx, w[k], id));
+        if (d->compute.empty()) {
+          compute_lookup(L, id, &values, nullptr);
+          d->compute = id;
+        }
+        c = values[idx > 0 ? idx - 1 : 0];
       } else
         sf::fail("Invalid attribute %s in dump local command", w[k].c_str());
       if (d->lcols.n >= kContactMaxCols) sf::fail("Illegal dump local command");
@@ -581,20 +546,7 @@ void dump_command(SfLammps& L, const std::vector<std::string>& w)
       long idx = 0;
       const std::string err = parse_compute_column(w[k], "custom", &id, &idx);
       if (!err.empty()) sf::fail("%s", err.c_str());
-      const int nc = atom_compute_ncols(L, id);
-      if (nc == 0 && pair_local_exists(L, id))
-        sf::fail("Dump custom compute does not compute per-atom info: %s is a compute pair/local (dump local prints its "
-                 "rows)", id.c_str());
-      if (nc == 0 && global_compute_nvalues(L, id) > 0)
-        sf::fail("Dump custom compute does not compute per-atom info: %s is a global compute (fix ave/time and thermo print it)",
-                 id.c_str());
-      if (nc == 0 && rdf_array_rows(L, id) > 0)
-        sf::fail("Dump custom compute does not compute per-atom info: %s is a global array (fix ave/time mode vector prints it)",
-                 id.c_str());
-      if (nc == 0) sf::fail("Could not find dump custom compute ID %s", id.c_str());
-      if (idx == 0 && nc != 1) sf::fail("Dump custom compute does not compute per-atom vector: %s", w[k].c_str());
-      if (idx > 0 && nc == 1) sf::fail("Dump custom compute does not compute per-atom array: %s", w[k].c_str());
-      if (idx > nc) sf::fail("Dump custom compute vector is accessed out-of-range: %s", w[k].c_str());
+      fail_if(check_dump_custom(compute_shape(L, id), idx, w[k], id));
       if (L.world_size > 1 || L.decomposed || L.eng.nranks() > 1 || L.eng.decomposed())
         sf::fail("dump custom: c_ columns on one rank only (no decomposed domain)");
       if ((int)d->xid.size() >= kMaxXCols) sf::fail("dump custom: more than %d c_ columns", kMaxXCols);

@@ -1,7 +1,7 @@
 // sf_global.h -- the global computes `compute ID group reduce MODE input ...`, `compute ID group ke` and `compute ID group
 // erotate/sphere`, and `fix ID group ave/time Nevery Nrepeat Nfreq c_ID ...` (sf_global.hip): one number per step that the
 // user chooses, reduced over the whole bed on the GPU and written as a time series.  The computes share the ID space of the
-// other computes (compute_command of sf_contacts.hip hands the styles over); the fix shares the ID space of the other
+// other computes (sf_compute_ids.h: they plug in there as global_compute_kind()); the fix shares the ID space of the other
 // averaging fixes (sf_ave_fix.h).
 #pragma once
 #include <string>
@@ -11,16 +11,10 @@ namespace sf {
 struct SfLammps;
 
 // ---- the computes ----
-bool global_compute_style(const std::string& style);
-// `compute ID group STYLE ...` of such a style (the caller has checked that the ID is new)
-void global_compute_define(SfLammps& L, const std::vector<std::string>& w);
-// the length of global compute `id` (1 for a scalar), whether it is a vector (`c_ID[k]`) and extensive; 0: no such compute
-int global_compute_nvalues(const SfLammps& L, const std::string& id, bool* is_vector = nullptr, bool* extensive = nullptr);
-void global_compute_remove(SfLammps& L, const std::string& id);
+// is global compute `id` extensive (thermo divides such a value by the atom count under norm yes)?
+bool global_compute_extensive(const SfLammps& L, const std::string& id);
 // does a compute reduce name compute `id` as an input?
 bool reduce_uses_compute(const SfLammps& L, const std::string& id);
-// the state changed at an unchanged step: evaluate again when asked next (atom_compute_invalidate calls it)
-void global_invalidate(SfLammps& L);
 // the values of `id` on the state as it stands, on the host (evaluated first when they are stale; one copy, one wait)
 void global_values_host(SfLammps& L, const std::string& id, std::vector<double>* out);
 // ... and where they lie on the device (evaluated first when they are stale; no copy, no wait): nvalues doubles that stay

@@ -44,8 +44,8 @@
 #include "sf_atom_terms.h"
 #include "sf_ave_fix.h"
 #include "sf_block_reduce.h"
-#include "sf_chunk.h"
 #include "sf_compute_atom.h"
+#include "sf_compute_ids.h"
 #include "sf_contacts.h"
 #include "sf_displace.h"
 #include "sf_displace_parse.h"
@@ -289,9 +289,7 @@ struct GlobalCompute {
   ReduceSpec S;
   int nvalues = 1;
   int slot = -1;   // in the pool
-  // what the values were made at (-1: nothing)
-  long long step = -1, nbuilds = -1;
-  int nlocal = -1;
+  StateStamp made;   // what the values were made at
   bool unwrapped() const { return kind == G_COM; }
   bool is_vector() const { return unwrapped() || (kind == G_REDUCE && S.inputs.size() > 1); }
   bool extensive() const { return !unwrapped() && (kind != G_REDUCE || S.mode == GM_SUM || S.mode == GM_SUMSQ); }
@@ -367,51 +365,18 @@ struct GlobalSet {
   }
 };
 
-GlobalSet* set_of(const SfLammps& L) { return static_cast<GlobalSet*>(L.globals); }
-GlobalSet& ensure_set(SfLammps& L)
-{
-  if (!L.globals) {
-    L.globals = new GlobalSet();
-    L.globals_delete = [](void* p) { delete static_cast<GlobalSet*>(p); };
-  }
-  return *set_of(L);
-}
+GlobalSet* set_of(const SfLammps& L) { return L.globals.get<GlobalSet>(); }
+GlobalSet& ensure_set(SfLammps& L) { return L.globals.ensure<GlobalSet>(); }
 
 std::string who_of(const GlobalCompute& c) { return std::string("compute ") + kStyleName[c.kind]; }
 
-bool fresh(const SfLammps& L, const GlobalCompute& c)
-{
-  const DemEngine& e = L.eng;
-  return c.step == e.nsteps() && c.nbuilds == e.nbuilds() && c.nlocal == e.nlocal();
-}
-
 // a c_ input of compute reduce: checked at the compute line and again at every evaluation (the compute may have been
 // removed and defined anew).  Returns true for a compute pair/local, false for a per-atom compute
-bool check_reduce_input(const SfLammps& L, const ReduceInput& in)
+bool reduce_input_is_local(const SfLammps& L, const ReduceInput& in)
 {
-  const int nc = atom_compute_ncols(L, in.id);
-  if (nc > 0) {
-    if (in.index == 0 && nc != 1) fail("Compute reduce compute does not calculate a per-atom vector");
-    if (in.index > 0 && nc == 1) fail("Compute reduce compute does not calculate a per-atom array");
-    if (in.index > nc) fail("Compute reduce compute array is accessed out-of-range");
-    return false;
-  }
-  if (pair_local_exists(L, in.id)) {
-    std::vector<unsigned char> values;
-    compute_lookup(L, in.id, &values, nullptr);
-    const long nv = (long)values.size();
-    if (in.index == 0 && nv != 1) fail("Compute reduce compute does not calculate a local vector");
-    if (in.index > 0 && nv == 1) fail("Compute reduce compute does not calculate a local array");
-    if (in.index > nv) fail("Compute reduce compute array is accessed out-of-range");
-    return true;
-  }
-  if (global_compute_nvalues(L, in.id) > 0)
-    fail("Compute reduce compute calculates global values (c_%s is a global compute: per-atom and local ones are reduced)",
-         in.id.c_str());
-  if (rdf_array_rows(L, in.id) > 0)
-    fail("Compute reduce compute calculates global values (c_%s is a global array: per-atom and local ones are reduced)",
-         in.id.c_str());
-  fail("Compute ID for compute reduce does not exist");
+  const ComputeShape shape = compute_shape(L, in.id);
+  fail_if(check_reduce_input(shape, in.index, in.id));
+  return shape.kind == CK_LOCAL;
 }
 
 // ---- the plan ----
@@ -545,7 +510,7 @@ void evaluate(SfLammps& L, GlobalSet& G, const std::vector<GlobalCompute*>& want
   for (GlobalCompute* c : want) {
     refuse_decomposed(L, who_of(*c).c_str());
     if (std::find(stale.begin(), stale.end(), c) != stale.end()) continue;
-    if (fresh(L, *c)) continue;
+    if (c->made.is_now(e)) continue;
     stale.push_back(c);
   }
   for (const AccReq& a : accs)
@@ -571,7 +536,7 @@ void evaluate(SfLammps& L, GlobalSet& G, const std::vector<GlobalCompute*>& want
         pc.ave = c->S.mode == GM_AVE || c->S.mode == GM_AVESQ;
         if (in.attr != AA_COMPUTE) {
           pc.col.set(in.attr < AA_VX ? GS_XR : (in.attr < AA_FX ? GS_VM : GS_FORCE), in.attr % 3, op);
-        } else if (!check_reduce_input(L, in)) {
+        } else if (!reduce_input_is_local(L, in)) {
           int nc = 0;
           const double* val = atom_compute_values(L, in.id, &nc);   // (once per step however many ask)
           pc.col.set(GS_PTR, 0, op);
@@ -611,11 +576,7 @@ void evaluate(SfLammps& L, GlobalSet& G, const std::vector<GlobalCompute*>& want
     launch_columns(L, G, rc.second, R.n, true, &late);   // (before the next compute's rows take the same buffers)
   }
   launch_late_acc(L, G, late);
-  for (GlobalCompute* c : stale) {
-    c->step = e.nsteps();
-    c->nbuilds = e.nbuilds();
-    c->nlocal = n;
-  }
+  for (GlobalCompute* c : stale) c->made.set(e);
 }
 
 void copy_to_host(SfLammps& L, GlobalSet& G, int slot, int n, bool zero_after)
@@ -632,32 +593,17 @@ void copy_to_host(SfLammps& L, GlobalSet& G, int slot, int n, bool zero_after)
 // checked at the fix line and again at every sample (the compute may have been redefined)
 void check_fix_value(const SfLammps& L, const AveTimeValue& v)
 {
-  bool vec = false;
-  const int n = global_compute_nvalues(L, v.id, &vec);
-  if (n == 0) {
-    if (atom_compute_ncols(L, v.id) > 0 || pair_local_exists(L, v.id) || rdf_array_rows(L, v.id) > 0)
-      fail(v.index == 0 ? "Fix ave/time compute does not calculate a scalar" : "Fix ave/time compute does not calculate a vector");
-    fail("Compute ID for fix ave/time does not exist");
-  }
-  if (v.index == 0 && vec) fail("Fix ave/time compute does not calculate a scalar");
-  if (v.index > 0 && !vec) fail("Fix ave/time compute does not calculate a vector");
-  if (v.index > n) fail("Fix ave/time compute vector is accessed out-of-range");
+  fail_if(check_ave_time_scalar(compute_shape(L, v.id), v.index));
 }
 
 // mode vector: c_ID[k] is column k of a global array; every value of a fix has the same number of rows, which is returned.
 // Checked at the fix line and again at every sample
-int check_fix_column(const SfLammps& L, const AveTimeValue& v, int nrows)
+int check_fix_column(const SfLammps& L, const AveTimeValue& v, int nrows, int* ncols = nullptr)
 {
-  int ncols = 0;
-  const int rows = rdf_array_rows(L, v.id, &ncols);
-  if (rows == 0) {
-    if (global_compute_nvalues(L, v.id) > 0 || atom_compute_ncols(L, v.id) > 0 || pair_local_exists(L, v.id))
-      fail("Fix ave/time compute does not calculate an array");
-    fail("Compute ID for fix ave/time does not exist");
-  }
-  if (v.index > ncols) fail("Fix ave/time compute array is accessed out-of-range");
-  if (nrows > 0 && rows != nrows) fail("Fix ave/time columns must all be the same length");
-  return rows;
+  const ComputeShape shape = compute_shape(L, v.id);
+  fail_if(check_ave_time_vector(shape, v.index, nrows));
+  if (ncols) *ncols = shape.n;
+  return shape.rows;
 }
 
 void write_line(AveTimeFix& F)
@@ -759,25 +705,17 @@ GlobalCompute& compute_of(GlobalSet& G, const std::string& id, const char* missi
   return *c;
 }
 
-}  // namespace
+// ---- the computes: the kind (sf_compute_ids.h) ----
 
-const AveFixKind& ave_time_kind()
+bool is_style(const std::string& style)
 {
-  static const AveFixKind kind = {"fix ave/time", fix_exists, unfix, fix_uses_compute, next_step};
-  return kind;
-}
-
-// ---- the computes ----
-
-bool global_compute_style(const std::string& style)
-{
-  if (style == "reduce/region") return true;   // (refused by name in global_compute_define)
+  if (style == "reduce/region") return true;   // (refused by name in define)
   for (const char* s : kStyleName)
     if (style == s) return true;
   return false;
 }
 
-void global_compute_define(SfLammps& L, const std::vector<std::string>& w)
+void define(SfLammps& L, const std::vector<std::string>& w)
 {
   if (w[3] == "reduce/region") fail("compute reduce/region is not supported: compute reduce on a region group is (group ID region RID, or group ID dynamic)");
   auto c = std::make_unique<GlobalCompute>();
@@ -789,7 +727,7 @@ void global_compute_define(SfLammps& L, const std::vector<std::string>& w)
   if (c->kind == G_REDUCE) {
     fail_if(parse_reduce(w, &c->S));
     for (const ReduceInput& in : c->S.inputs)
-      if (in.attr == AA_COMPUTE) check_reduce_input(L, in);
+      if (in.attr == AA_COMPUTE) reduce_input_is_local(L, in);
     c->nvalues = (int)c->S.inputs.size();
   } else if (c->kind == G_COM) {
     fail_if(parse_com(w));
@@ -802,27 +740,50 @@ void global_compute_define(SfLammps& L, const std::vector<std::string>& w)
   G.computes.push_back(std::move(c));
 }
 
-int global_compute_nvalues(const SfLammps& L, const std::string& id, bool* is_vector, bool* extensive)
+bool shape(const SfLammps& L, const std::string& id, ComputeShape* s)
 {
   GlobalSet* G = set_of(L);
   const GlobalCompute* c = G ? G->find(id) : nullptr;
-  if (!c) return 0;
-  if (is_vector) *is_vector = c->is_vector();
-  if (extensive) *extensive = c->extensive();
-  return c->nvalues;
+  if (!c) return false;
+  *s = ComputeShape();
+  s->kind = CK_GLOBAL;
+  s->n = c->nvalues;
+  s->vector = c->is_vector();
+  return true;
 }
 
-void global_compute_remove(SfLammps& L, const std::string& id)
+void remove(SfLammps& L, const std::string& id)
 {
   GlobalSet* G = set_of(L);
-  if (!G) return;
-  for (size_t k = 0; k < G->computes.size(); k++)
-    if (G->computes[k]->id == id) {
-      SF_HIP(hipStreamSynchronize(L.eng.stream()));   // (a launch queued on the stream may still write its values)
-      G->give(G->computes[k]->slot, G->computes[k]->nvalues);
-      G->computes.erase(G->computes.begin() + k);
-      return;
-    }
+  // (a launch queued on the stream may still write its values)
+  if (const std::unique_ptr<GlobalCompute> c = G ? compute_take(L, G->computes, id) : nullptr) G->give(c->slot, c->nvalues);
+}
+
+void invalidate(SfLammps& L)
+{
+  if (GlobalSet* G = set_of(L))
+    for (auto& c : G->computes) c->made.clear();
+}
+
+}  // namespace
+
+const AveFixKind& ave_time_kind()
+{
+  static const AveFixKind kind = {"fix ave/time", fix_exists, unfix, fix_uses_compute, next_step};
+  return kind;
+}
+
+const ComputeKindOps& global_compute_kind()
+{
+  static const ComputeKindOps kind = {is_style, define, remove, shape, invalidate};
+  return kind;
+}
+
+bool global_compute_extensive(const SfLammps& L, const std::string& id)
+{
+  GlobalSet* G = set_of(L);
+  const GlobalCompute* c = G ? G->find(id) : nullptr;
+  return c && c->extensive();
 }
 
 bool reduce_uses_compute(const SfLammps& L, const std::string& id)
@@ -834,12 +795,6 @@ bool reduce_uses_compute(const SfLammps& L, const std::string& id)
       for (const ReduceInput& in : c->S.inputs)
         if (in.attr == AA_COMPUTE && in.id == id) return true;
   return false;
-}
-
-void global_invalidate(SfLammps& L)
-{
-  if (GlobalSet* G = set_of(L))
-    for (auto& c : G->computes) c->step = -1;
 }
 
 void global_values_host(SfLammps& L, const std::string& id, std::vector<double>* out)
@@ -918,9 +873,8 @@ void global_step_due(SfLammps& L, const std::vector<std::string>& also)
       const int nv = (int)f->S.values.size();
       for (int j = 0; j < nv; j++) {
         const AveTimeValue& v = f->S.values[j];
-        check_fix_column(L, v, f->nrows);
         int ncols = 0;
-        rdf_array_rows(L, v.id, &ncols);
+        check_fix_column(L, v, f->nrows, &ncols);
         const double* src = rdf_array_device(L, v.id);
         k_global_col_acc<<<div_up(f->nrows, kGBlock), kGBlock, 0, L.eng.stream()>>>(src + (v.index - 1), ncols, f->nrows,
                                                                                     f->vacc + j, nv);
@@ -955,18 +909,10 @@ long long sf_lammps_compute_global(void* ptr, const char* id, long long max, dou
   SF_API_BEGIN
   sf::SfLammps& L = *handle(ptr);
   if (!id) sf::fail("sf_lammps_compute_global: null argument");
-  bool vec = false;
-  n = sf::global_compute_nvalues(L, id, &vec);
-  if (n == 0) {
-    if (sf::atom_compute_ncols(L, id) > 0 || sf::pair_local_exists(L, id))
-      sf::fail("compute %s does not calculate a global scalar or vector (sf_lammps_compute_atom and sf_lammps_get_contacts "
-               "return per-atom and local values)", id);
-    if (sf::rdf_array_rows(L, id) > 0)
-      sf::fail("compute %s does not calculate a global scalar or vector (it is a global array: sf_lammps_compute_array returns "
-               "it)", id);
-    sf::fail("Could not find compute ID %s", id);
-  }
-  if (is_vector) *is_vector = vec ? 1 : 0;
+  const sf::ComputeShape shape = sf::compute_shape(L, id);
+  sf::fail_if(sf::check_get_global(shape, id));
+  n = shape.n;
+  if (is_vector) *is_vector = shape.vector ? 1 : 0;
   if (n <= max) {
     if (!values) sf::fail("sf_lammps_compute_global: null argument");
     std::vector<double> v;
@@ -1045,7 +991,7 @@ int sf_lammps_global_cost(void* ptr, const char* id, double* ms)
   if (!c) sf::fail("Could not find compute ID %s", id);
   // (the per-atom computes behind c_ inputs are evaluated outside the time: sf_lammps_compute_atom_cost times them)
   sf::evaluate(L, *G, {c}, {});
-  c->step = -1;
+  c->made.clear();
   *ms = sf::stream_ms(L.eng.stream(), [&] { sf::evaluate(L, *G, {c}, {}); });
   SF_API_END(0)
 }

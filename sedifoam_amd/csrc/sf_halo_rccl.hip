@@ -269,8 +269,6 @@ struct HaloComm {
   }
 };
 
-static void halo_deleter(void* p) { delete static_cast<HaloComm*>(p); }
-
 // ------------------------------------------------------------------------------------------------
 // The slab driver in C++: rebuild-time exchanges ([3P] Comm::exchange / Comm::borders, the migration payload of
 // fix_fluid_drag.cpp:211-243 + wall and pair history) and the lammps_step loop over RCCL, so that an MPI / C++ host
@@ -1471,7 +1469,7 @@ static CloudSlab cloud_slab(void* cloud)
   void* lmp = nullptr;
   if (sf_cloud_slab_info(cloud, &lmp, C.n, &C.nxg, &C.per_x, &C.smoothing) != 0) fail("%s", last_error().c_str());
   C.L = static_cast<SfLammps*>(lmp);
-  C.hc = static_cast<HaloComm*>(C.L->halo);
+  C.hc = C.L->halo.get<HaloComm>();
   if (!C.hc || !C.hc->comm || C.hc->brick) fail("sf_cloud_slab_*: the engine has no slab communicator (sf_slab_init first)");
   if (C.nxg <= 0) fail("sf_cloud_slab_*: not a slab mesh (sf_cloud_mesh.slab_nx_global)");
   const int W = C.hc->world, r = C.hc->rank;
@@ -1578,7 +1576,7 @@ static SfLammps* H(void* p)
 size_t sf::dump_gather(SfLammps& L, const char* src, size_t nbytes, unsigned long long count, char** dst, size_t* cap,
                        unsigned long long* count_total)
 {
-  auto* hc = static_cast<HaloComm*>(L.halo);
+  auto* hc = L.halo.get<HaloComm>();
   if (!hc || !hc->comm) fail("dump: a single file on %d ranks needs the engine's communicator (the bricks of read_data)",
                              L.world_size);
   const int W = hc->world, r = hc->rank;
@@ -1636,10 +1634,8 @@ int sf_dem_comm_init(void* ptr, const char* id128, int rank, int world)
   SF_API_BEGIN
   SfLammps* L = H(ptr);
   if (world < 1 || rank < 0 || rank >= world) sf::fail("sf_dem_comm_init: rank %d of %d", rank, world);
-  if (L->halo && L->halo_delete) L->halo_delete(L->halo);   // (a second init replaces the communicator)
-  auto* hc = new sf::HaloComm();
-  L->halo = hc;
-  L->halo_delete = sf::halo_deleter;
+  L->halo.reset();   // (a second init replaces the communicator)
+  auto* hc = &L->halo.ensure<sf::HaloComm>();
   hc->rank = rank;
   hc->world = world;
   ncclUniqueId id;
@@ -1654,7 +1650,7 @@ int sf_dem_halo_run(void* ptr, int first_k, int n, const sf_halo_layout* lay, in
 {
   SF_API_BEGIN
   SfLammps* L = H(ptr);
-  auto* hc = static_cast<sf::HaloComm*>(L->halo);
+  auto* hc = L->halo.get<sf::HaloComm>();
   if (!hc || !hc->comm) sf::fail("sf_dem_halo_run: call sf_dem_comm_init first");
   if (!lay || !trigger) sf::fail("sf_dem_halo_run: null argument");
   if (lay->world != hc->world) sf::fail("sf_dem_halo_run: layout for %d ranks, communicator has %d", lay->world, hc->world);
@@ -1667,7 +1663,7 @@ int sf_slab_init(void* ptr, const char* id128, int rank, int world, double xlo, 
   SF_API_BEGIN
   SfLammps* L = H(ptr);
   if (sf_dem_comm_init(ptr, id128, rank, world) != 0) sf::fail("%s", sf::last_error().c_str());
-  auto* hc = static_cast<sf::HaloComm*>(L->halo);
+  auto* hc = L->halo.get<sf::HaloComm>();
   hc->slab = true;
   hc->periodic_x = periodic_x != 0;
   hc->box_lo = xlo;
@@ -1693,7 +1689,7 @@ int sf_brick_init(void* ptr, const char* id128, int rank, int world, int px, int
   SfLammps* L = H(ptr);
   if (px < 1 || py < 1 || pz < 1 || px * py * pz != world) sf::fail("sf_brick_init: %d x %d x %d bricks for %d ranks", px, py, pz, world);
   if (sf_dem_comm_init(ptr, id128, rank, world) != 0) sf::fail("%s", sf::last_error().c_str());
-  auto* hc = static_cast<sf::HaloComm*>(L->halo);
+  auto* hc = L->halo.get<sf::HaloComm>();
   hc->slab = true;
   hc->brick = new sf::BrickState();
   sf::BrickState& B = *hc->brick;
@@ -1786,7 +1782,7 @@ int sf_cloud_slab_phase(void* cloud, int phase)
 
 static sf::HaloComm* slab_of(SfLammps* L)
 {
-  auto* hc = static_cast<sf::HaloComm*>(L->halo);
+  auto* hc = L->halo.get<sf::HaloComm>();
   if (!hc || !hc->slab) sf::fail("sf_slab_*: call sf_slab_init first");
   return hc;
 }
@@ -1875,7 +1871,7 @@ int sf_slab_comm_info(void* ptr, int* comm_ranks, int* rccl_version, char* lib_p
 int sf_slab_active(void* ptr)
 {
   SF_API_BEGIN
-  auto* hc = static_cast<sf::HaloComm*>(H(ptr)->halo);
+  auto* hc = H(ptr)->halo.get<sf::HaloComm>();
   const int on = hc && hc->slab ? 1 : 0;
   SF_API_END(on)
 }
@@ -1883,7 +1879,7 @@ int sf_slab_active(void* ptr)
 int sf_slab_direct_halo(void* ptr)
 {
   SF_API_BEGIN
-  auto* hc = static_cast<sf::HaloComm*>(H(ptr)->halo);
+  auto* hc = H(ptr)->halo.get<sf::HaloComm>();
   const int on = hc && hc->direct && hc->direct->on ? hc->direct->mode : 0;   // (1: receive areas, 2: ghost slots)
   SF_API_END(on)
 }
@@ -1892,7 +1888,7 @@ int sf_slab_allreduce_sum(void* ptr, double* values, int n)
 {
   SF_API_BEGIN
   SfLammps* L = H(ptr);
-  auto* hc = static_cast<sf::HaloComm*>(L->halo);
+  auto* hc = L->halo.get<sf::HaloComm>();
   if (!hc || !hc->comm) sf::fail("sf_slab_allreduce_sum: no communicator (sf_slab_init / sf_brick_init first)");
   if (n < 0 || (n && !values)) sf::fail("sf_slab_allreduce_sum: bad arguments");
   if (hc->world > 1 && n > 0) {

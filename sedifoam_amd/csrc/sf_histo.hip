@@ -30,10 +30,10 @@
 #include "../../include/sedifoam_amd.h"
 #include "sf_ave_fix.h"
 #include "sf_compute_atom.h"
+#include "sf_compute_ids.h"
 #include "sf_contacts.h"
 #include "sf_gather_col.h"
 #include "sf_global.h"
-#include "sf_nbr.h"
 #include "sf_histo.h"
 
 // ((v - lo) * bininv stays a difference and a product, whatever the compiler would fuse around it: the bin of a value is
@@ -189,15 +189,8 @@ struct HistoSet {
   }
 };
 
-HistoSet* set_of(const SfLammps& L) { return static_cast<HistoSet*>(L.histos); }
-HistoSet& ensure_set(SfLammps& L)
-{
-  if (!L.histos) {
-    L.histos = new HistoSet();
-    L.histos_delete = [](void* p) { delete static_cast<HistoSet*>(p); };
-  }
-  return *set_of(L);
-}
+HistoSet* set_of(const SfLammps& L) { return L.histos.get<HistoSet>(); }
+HistoSet& ensure_set(SfLammps& L) { return L.histos.ensure<HistoSet>(); }
 
 // The kind of the values and every rule that needs the computes: checked at the fix line and again at every sample (a
 // compute may have been removed and defined anew)
@@ -205,13 +198,13 @@ int check_values(const SfLammps& L, const HistoSpec& S)
 {
   std::vector<int> kinds;
   for (const HistoValue& v : S.values) {
-    if (v.attr != AA_COMPUTE) kinds.push_back(HK_PERATOM);
-    else if (atom_compute_ncols(L, v.id) > 0) kinds.push_back(HK_PERATOM);
-    else if (pair_local_exists(L, v.id)) kinds.push_back(HK_LOCAL);
-    else if (global_compute_nvalues(L, v.id) > 0) kinds.push_back(HK_GLOBAL);
-    else if (rdf_array_rows(L, v.id) > 0)
-      fail("Fix ave/histo compute does not calculate a global scalar or vector (c_%s is a global array, which is not binned)", v.id.c_str());
-    else fail("Compute ID for fix ave/histo does not exist");
+    if (v.attr != AA_COMPUTE) {
+      kinds.push_back(HK_PERATOM);
+      continue;
+    }
+    const ComputeShape shape = compute_shape(L, v.id);
+    fail_if(check_ave_histo_kind(shape, v.id));
+    kinds.push_back(shape.kind == CK_PERATOM ? HK_PERATOM : (shape.kind == CK_LOCAL ? HK_LOCAL : HK_GLOBAL));
   }
   const int kind = kinds[0];
   for (int k : kinds)
@@ -221,33 +214,8 @@ int check_values(const SfLammps& L, const HistoSpec& S)
     fail("fix ave/histo: kind %s does not agree with the values, which are %s", names[S.kind], names[kind]);
   if (kind == HK_PERATOM && S.mode == HM_SCALAR) fail("Fix ave/histo cannot input per-atom values in scalar mode");
   if (kind == HK_LOCAL && S.mode == HM_SCALAR) fail("Fix ave/histo cannot input local values in scalar mode");
-  for (const HistoValue& v : S.values) {
-    if (v.attr != AA_COMPUTE) continue;
-    if (kind == HK_PERATOM) {
-      const int nc = atom_compute_ncols(L, v.id);
-      if (v.index == 0 && nc != 1) fail("Fix ave/histo compute does not calculate a per-atom vector");
-      if (v.index > 0 && nc == 1) fail("Fix ave/histo compute does not calculate a per-atom array");
-      if (v.index > nc) fail("Fix ave/histo compute array is accessed out-of-range");
-    } else if (kind == HK_LOCAL) {
-      std::vector<unsigned char> values;
-      compute_lookup(L, v.id, &values, nullptr);
-      const long nv = (long)values.size();
-      if (v.index == 0 && nv != 1) fail("Fix ave/histo compute does not calculate a local vector");
-      if (v.index > 0 && nv == 1) fail("Fix ave/histo compute does not calculate a local array");
-      if (v.index > nv) fail("Fix ave/histo compute array is accessed out-of-range");
-    } else {
-      bool vec = false;
-      const int n = global_compute_nvalues(L, v.id, &vec);
-      if (S.mode == HM_SCALAR) {
-        if (v.index == 0 && vec) fail("Fix ave/histo compute does not calculate a global scalar");
-        if (v.index > 0 && !vec) fail("Fix ave/histo compute does not calculate a global vector");
-        if (v.index > n) fail("Fix ave/histo compute vector is accessed out-of-range");
-      } else {
-        if (v.index > 0) fail("Fix ave/histo compute does not calculate a global array");   // (no compute here has one)
-        if (!vec) fail("Fix ave/histo compute does not calculate a global vector");
-      }
-    }
-  }
+  for (const HistoValue& v : S.values)
+    if (v.attr == AA_COMPUTE) fail_if(check_ave_histo_index(compute_shape(L, v.id), v.index, S.mode == HM_SCALAR));
   return kind;
 }
 
@@ -318,7 +286,7 @@ long long build_table(SfLammps& L, const HistoFix& F, const std::vector<int>& wh
         c.p = rv == CV_TAG1 ? rows.tag1 : rows.tag2;
       }   // (eng: 0)
     } else {
-      const int len = global_compute_nvalues(L, v.id);
+      const int len = compute_shape(L, v.id).n;
       const double* val = global_values_device(L, v.id);   // (fresh when global_step_due has run at this step)
       c.set(GS_PTR, 0, 0);
       if (F.S.mode == HM_SCALAR) {

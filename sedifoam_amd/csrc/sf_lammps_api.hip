@@ -17,8 +17,7 @@
 #include "../../include/sedifoam_amd.h"
 #include "sf_ave_fix.h"
 #include "sf_chunk.h"
-#include "sf_compute_atom.h"
-#include "sf_contacts.h"
+#include "sf_compute_ids.h"
 #include "sf_dump.h"
 #include "sf_env.h"
 #include "sf_feed.h"
@@ -220,7 +219,7 @@ namespace sf {
 void particles_change_begin(SfLammps& L, const char* who, bool creating)
 {
   if (L.eng.rigid_on()) fail("%s: not while fix rigid/nve exists (its bodies are fixed sets of atoms)", who);
-  atom_compute_invalidate(L);
+  computes_invalidate(L);
   if (creating && L.world_size == 1 && !L.decomposed && !L.eng.decomposed()) (void)L.eng.images_enable();
 }
 
@@ -571,7 +570,7 @@ void command(SfLammps& L, const std::string& line)
   std::vector<std::string> w = split(line);
   if (w.empty()) return;
   const std::string& c = w[0];
-  sf::atom_compute_invalidate(L);   // (a command may change the state at an unchanged step: `velocity`, `pair_style`, a fix)
+  sf::computes_invalidate(L);   // (a command may change the state at an unchanged step: `velocity`, `pair_style`, a fix)
   if (sf::thermo_command(L, w)) return;   // thermo, thermo_style, thermo_modify, log, echo (sf_thermo.hip)
   if (c == "units") {
     if (w.size() != 2 || (w[1] != "lj" && w[1] != "si")) sf::fail("units %s not supported (lj | si: nktv2p = 1)", w.size() > 1 ? w[1].c_str() : "");
@@ -1009,7 +1008,7 @@ int sf_dem_create_atoms(void* ptr, int n, const double* x, const double* v, cons
                         const double* diameter, const double* density, const int* tag, const int* type)
 {
   SF_API_BEGIN
-  sf::atom_compute_invalidate(*H(ptr));
+  sf::computes_invalidate(*H(ptr));
   H(ptr)->eng.create_atoms(n, x, v, omega, diameter, density, tag, type);
   SF_API_END(0)
 }

@@ -32,9 +32,7 @@
 
 #include "../../include/sedifoam_amd.h"
 #include "sf_compute_atom.h"
-#include "sf_contacts.h"
-#include "sf_global.h"
-#include "sf_handles.h"
+#include "sf_compute_ids.h"
 #include "sf_nbr.h"
 #include "sf_unmap.h"
 
@@ -270,29 +268,6 @@ __global__ __launch_bounds__(kNBlock) void k_nbr_coord(NbrGridDev G, const doubl
 
 // ---- host side ----
 
-struct Grown {   // device scratch, grown geometrically (no allocation per evaluation once it has grown)
-  void* p = nullptr;
-  size_t n = 0;
-  void* get(size_t need, hipStream_t s)
-  {
-    if (need > n) {
-      if (p) {
-        SF_HIP(hipStreamSynchronize(s));
-        SF_HIP(hipFree(p));
-      }
-      n = need + need / 4 + 4096;
-      SF_HIP(hipMalloc(&p, n));
-    }
-    return p;
-  }
-  template <class T>
-  T* as() const { return static_cast<T*>(p); }
-  ~Grown()
-  {
-    if (p) (void)hipFree(p);
-  }
-};
-
 struct RawTmp {   // the scratch of the sort and scan wrappers of sf_sort.hip, which grow it themselves
   void* p = nullptr;
   size_t n = 0;
@@ -306,11 +281,9 @@ struct NbrGrid {
   double rc = 0.0;
   NbrGridDev D{};
   int ncells = 1;
-  Grown key_in, idx_in, key_out, idx_out, count, start, pos;
+  DeviceScratch key_in, idx_in, key_out, idx_out, count, start, pos;
   RawTmp sort_tmp, scan_tmp;
-  // what it was made at (-1: nothing)
-  long long step = -1, nbuilds = -1;
-  int nlocal = -1;
+  StateStamp made;   // what it was made at
 };
 
 struct RdfCompute {
@@ -321,8 +294,7 @@ struct RdfCompute {
   int4* d_pairs = nullptr;
   unsigned long long* d_acc = nullptr;   // [npairs * nbin + 3 * npairs]
   double* d_out = nullptr;               // [nbin][1 + 2 npairs]
-  long long step = -1, nbuilds = -1;
-  int nlocal = -1;
+  StateStamp made;
   int npairs() const { return (int)S.pairs.size(); }
   int ncols() const { return 1 + 2 * npairs(); }
   size_t nacc() const { return (size_t)npairs() * (size_t)S.nbin + 3 * (size_t)npairs(); }
@@ -339,7 +311,7 @@ constexpr size_t kMaxGrids = 4;   // distinct cutoffs kept at once
 struct NbrSet {
   std::vector<std::unique_ptr<RdfCompute>> computes;
   std::vector<std::unique_ptr<NbrGrid>> grids;
-  Grown cost_val;   // sf_lammps_nbr_cost of a compute coord/atom: where its columns go
+  DeviceScratch cost_val;   // sf_lammps_nbr_cost of a compute coord/atom: where its columns go
   long long grid_builds = 0, launches = 0, host_copies = 0;
   RdfCompute* find(const std::string& id)
   {
@@ -349,15 +321,8 @@ struct NbrSet {
   }
 };
 
-NbrSet* set_of(const SfLammps& L) { return static_cast<NbrSet*>(L.nbr); }
-NbrSet& ensure_set(SfLammps& L)
-{
-  if (!L.nbr) {
-    L.nbr = new NbrSet();
-    L.nbr_delete = [](void* p) { delete static_cast<NbrSet*>(p); };
-  }
-  return *set_of(L);
-}
+NbrSet* set_of(const SfLammps& L) { return L.nbr.get<NbrSet>(); }
+NbrSet& ensure_set(SfLammps& L) { return L.nbr.ensure<NbrSet>(); }
 
 // The cells of cutoff rc over the box as it is now: at least rc (1 + 2^-20) wide, so that the rounding of a cell index
 // (2^-52 of it) cannot put two atoms closer than rc into cells that are not adjacent; at most 2 n + 64 of them (a box that is
@@ -434,9 +399,7 @@ void build_grid(SfLammps& L, NbrSet& T, NbrGrid& g, const NbrGridDev& D, int nce
   }
   T.launches++;
   T.grid_builds++;
-  g.step = e.nsteps();
-  g.nbuilds = e.nbuilds();
-  g.nlocal = n;
+  g.made.set(e);
 }
 
 // the grid of cutoff rc on the state as it stands: kept with the step, the rebuild count, the atom count and the cell
@@ -457,9 +420,7 @@ NbrGrid& grid_of(SfLammps& L, NbrSet& T, const char* who, double rc, bool force 
     g = T.grids.back().get();
     g->rc = rc;
   }
-  const DemEngine& e = L.eng;
-  const bool same = g->step == e.nsteps() && g->nbuilds == e.nbuilds() && g->nlocal == e.nlocal() &&
-                    std::memcmp(&g->D, &D, sizeof(D)) == 0;
+  const bool same = g->made.is_now(L.eng) && std::memcmp(&g->D, &D, sizeof(D)) == 0;
   if (!same || force) build_grid(L, T, *g, D, ncells);
   return *g;
 }
@@ -485,16 +446,13 @@ void rdf_walk(SfLammps& L, NbrSet& T, RdfCompute& c, const NbrGrid& g)
 void rdf_evaluate(SfLammps& L, NbrSet& T, RdfCompute& c)
 {
   nbr_refuse_unsupported(L, "compute rdf");
-  const DemEngine& e = L.eng;
-  if (c.step == e.nsteps() && c.nbuilds == e.nbuilds() && c.nlocal == e.nlocal()) {
+  if (c.made.is_now(L.eng)) {
     int ncells = 1;
     (void)make_cells(L, "compute rdf", c.S.rc, &ncells);   // (the box check, also where the values are fresh)
     return;
   }
   rdf_walk(L, T, c, grid_of(L, T, "compute rdf", c.S.rc));
-  c.step = e.nsteps();
-  c.nbuilds = e.nbuilds();
-  c.nlocal = e.nlocal();
+  c.made.set(L.eng);
 }
 
 CoordArgs coord_args(int groupbit, double rc, const std::vector<TypeRange>& ranges)
@@ -528,13 +486,11 @@ RdfCompute& rdf_of(SfLammps& L, const std::string& id)
   return *c;
 }
 
-}  // namespace
+// ---- the kind (sf_compute_ids.h) ----
 
-void nbr_refuse_unsupported(const SfLammps& L, const char* who) { refuse_decomposed(L, who); }
+bool is_style(const std::string& style) { return style == "rdf"; }
 
-bool rdf_compute_style(const std::string& style) { return style == "rdf"; }
-
-void rdf_compute_define(SfLammps& L, const std::vector<std::string>& w)
+void define(SfLammps& L, const std::vector<std::string>& w)
 {
   auto c = std::make_unique<RdfCompute>();
   c->id = w[1];
@@ -556,25 +512,40 @@ void rdf_compute_define(SfLammps& L, const std::vector<std::string>& w)
   ensure_set(L).computes.push_back(std::move(c));
 }
 
-int rdf_array_rows(const SfLammps& L, const std::string& id, int* ncols)
+bool shape(const SfLammps& L, const std::string& id, ComputeShape* s)
 {
   NbrSet* T = set_of(L);
   const RdfCompute* c = T ? T->find(id) : nullptr;
-  if (!c) return 0;
-  if (ncols) *ncols = c->ncols();
-  return (int)c->S.nbin;
+  if (!c) return false;
+  *s = ComputeShape();
+  s->kind = CK_ARRAY;
+  s->n = c->ncols();
+  s->rows = (int)c->S.nbin;
+  return true;
 }
 
-void rdf_compute_remove(SfLammps& L, const std::string& id)
+void remove(SfLammps& L, const std::string& id)
 {
-  NbrSet* T = set_of(L);
-  if (!T) return;
-  for (size_t k = 0; k < T->computes.size(); k++)
-    if (T->computes[k]->id == id) {
-      SF_HIP(hipStreamSynchronize(L.eng.stream()));   // (a launch queued on the stream may still write its values)
-      T->computes.erase(T->computes.begin() + k);
-      return;
-    }
+  if (NbrSet* T = set_of(L)) compute_take(L, T->computes, id);   // (a launch queued on the stream may still write its values)
+}
+
+// (and the grids, which the walks of compute coord/atom share)
+void invalidate(SfLammps& L)
+{
+  if (NbrSet* T = set_of(L)) {
+    for (auto& c : T->computes) c->made.clear();
+    for (auto& g : T->grids) g->made.clear();
+  }
+}
+
+}  // namespace
+
+void nbr_refuse_unsupported(const SfLammps& L, const char* who) { refuse_decomposed(L, who); }
+
+const ComputeKindOps& rdf_compute_kind()
+{
+  static const ComputeKindOps kind = {is_style, define, remove, shape, invalidate};
+  return kind;
 }
 
 const double* rdf_array_device(SfLammps& L, const std::string& id)
@@ -592,14 +563,6 @@ void nbr_coord_atom(SfLammps& L, const char* who, int groupbit, double rc, const
   coord_walk(L, T, g, coord_args(groupbit, rc, ranges), val);
 }
 
-void nbr_invalidate(SfLammps& L)
-{
-  if (NbrSet* T = set_of(L)) {
-    for (auto& c : T->computes) c->step = -1;
-    for (auto& g : T->grids) g->step = -1;
-  }
-}
-
 }  // namespace sf
 
 using sf::handle;
@@ -612,15 +575,10 @@ long long sf_lammps_compute_array(void* ptr, const char* id, long long max, doub
   SF_API_BEGIN
   sf::SfLammps& L = *handle(ptr);
   if (!id) sf::fail("sf_lammps_compute_array: null argument");
-  int nc = 0;
-  const int rows = sf::rdf_array_rows(L, id, &nc);
-  if (rows == 0) {
-    if (sf::atom_compute_ncols(L, id) > 0 || sf::pair_local_exists(L, id) || sf::global_compute_nvalues(L, id) > 0)
-      sf::fail("compute %s does not calculate a global array (compute rdf does)", id);
-    sf::fail("Could not find compute ID %s", id);
-  }
-  if (ncols) *ncols = nc;
-  n = (long long)rows * nc;
+  const sf::ComputeShape shape = sf::compute_shape(L, id);
+  sf::fail_if(sf::check_get_array(shape, id));
+  if (ncols) *ncols = shape.n;
+  n = (long long)shape.rows * shape.n;
   if (n <= max) {
     if (!values) sf::fail("sf_lammps_compute_array: null argument");
     const double* d = sf::rdf_array_device(L, id);
@@ -639,8 +597,10 @@ long long sf_lammps_rdf_counts(void* ptr, const char* id, long long max, long lo
   SF_API_BEGIN
   sf::SfLammps& L = *handle(ptr);
   if (!id) sf::fail("sf_lammps_rdf_counts: null argument");
-  if (sf::rdf_array_rows(L, id) == 0) sf::fail("Could not find compute rdf ID %s", id);
-  sf::RdfCompute& c = sf::rdf_of(L, id);
+  sf::NbrSet* T = sf::set_of(L);
+  sf::RdfCompute* found = T ? T->find(id) : nullptr;
+  if (!found) sf::fail("Could not find compute rdf ID %s", id);
+  sf::RdfCompute& c = *found;
   if (npairs) *npairs = c.npairs();
   n = (long long)c.npairs() * c.S.nbin;
   if (n <= max) {
@@ -680,9 +640,7 @@ int sf_lammps_nbr_cost(void* ptr, const char* id, double* grid_ms, double* walk_
     sf::NbrGrid* g = nullptr;
     *grid_ms = sf::stream_ms(st, [&] { g = &sf::grid_of(L, T, "compute rdf", c->S.rc, true); });
     *walk_ms = sf::stream_ms(st, [&] { sf::rdf_walk(L, T, *c, *g); });
-    c->step = L.eng.nsteps();
-    c->nbuilds = L.eng.nbuilds();
-    c->nlocal = L.eng.nlocal();
+    c->made.set(L.eng);
   } else {
     int groupbit = 1;
     double rc = 0.0;

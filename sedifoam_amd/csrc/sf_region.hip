@@ -16,7 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/sedifoam_amd.h"
-#include "sf_compute_atom.h"
+#include "sf_compute_ids.h"
 #include "sf_region.h"
 #include "sf_region_parse.h"
 
@@ -160,16 +160,8 @@ struct Regions {
   }
 };
 
-const Regions* set_of(const SfLammps& L) { return static_cast<const Regions*>(L.regions); }
-
-Regions& regions_of(SfLammps& L)
-{
-  if (!L.regions) {
-    L.regions = new Regions();
-    L.regions_delete = [](void* p) { delete static_cast<Regions*>(p); };
-  }
-  return *static_cast<Regions*>(L.regions);
-}
+const Regions* set_of(const SfLammps& L) { return L.regions.get<Regions>(); }
+Regions& regions_of(SfLammps& L) { return L.regions.ensure<Regions>(); }
 
 void device_ready(SfLammps& L, Regions& R)
 {
@@ -233,7 +225,7 @@ void update(SfLammps& L, Regions& R, const std::vector<const DynGroup*>& due)
   device_ready(L, R);
   launch_update(L, R, due, L.eng.d_mask(), R.d_count);
   for (DynGroup& g : R.dyn) g.counted = true;   // (evaluated or only counted: every group's counter is its population now)
-  atom_compute_invalidate(L);   // (membership changed at an unchanged step: the per-atom, chunk and global computes ask again)
+  computes_invalidate(L);   // (membership changed at an unchanged step: the per-atom, chunk and global computes ask again)
 }
 
 const RegionDef& region_of(const Regions* R, const std::string& id, const char* missing)

@@ -970,18 +970,8 @@ struct Restart {
   }
 };
 
-void restart_delete(void* p) { delete static_cast<Restart*>(p); }
-
-Restart& ensure(SfLammps& L)
-{
-  if (!L.restart) {
-    L.restart = new Restart();
-    L.restart_delete = restart_delete;
-  }
-  return *static_cast<Restart*>(L.restart);
-}
-
-const Restart* peek(const SfLammps& L) { return static_cast<const Restart*>(L.restart); }
+Restart& ensure(SfLammps& L) { return L.restart.ensure<Restart>(); }
+const Restart* peek(const SfLammps& L) { return L.restart.get<Restart>(); }
 
 std::string with_step(const std::string& name, long long step)
 {
@@ -1045,7 +1035,7 @@ void write_begin(SfLammps& L, const std::string& file)
 
 void restart_drain(SfLammps& L)
 {
-  if (L.restart) static_cast<Restart*>(L.restart)->drain();
+  if (L.restart) L.restart.get<Restart>()->drain();
 }
 
 void write_restart_command(SfLammps& L, const std::string& file)
@@ -1115,7 +1105,7 @@ bool restart_active(const SfLammps& L)
 
 void restart_run_begin(SfLammps& L)
 {
-  Restart* R = static_cast<Restart*>(L.restart);
+  Restart* R = L.restart.get<Restart>();
   if (!R || R->pending.empty()) return;
   for (const RestartWall& w : R->pending) {
     const std::string msg = "WARNING: restart file: the saved state of fix " + w.id + " (" + std::to_string(w.tag.size()) +
@@ -1135,7 +1125,7 @@ long long restart_next_step(const SfLammps& L, long long step)
 
 void restart_write_due(SfLammps& L)
 {
-  Restart* R = static_cast<Restart*>(L.restart);
+  Restart* R = L.restart.get<Restart>();
   if (!R || R->every <= 0) return;
   const long long step = L.eng.nsteps();
   if (step % R->every != 0 || step == R->last_written) return;

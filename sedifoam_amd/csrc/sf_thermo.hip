@@ -27,12 +27,10 @@
 
 #include "../../include/sedifoam_amd.h"
 #include "sf_block_reduce.h"
-#include "sf_compute_atom.h"
-#include "sf_contacts.h"
+#include "sf_compute_ids.h"
 #include "sf_dem_dispatch.h"
 #include "sf_env.h"
 #include "sf_global.h"
-#include "sf_nbr.h"
 #include "sf_global_parse.h"
 #include "sf_handles.h"
 #include "sf_thermo.h"
@@ -258,15 +256,8 @@ struct Thermo {
   }
 };
 
-Thermo* get(const SfLammps& L) { return static_cast<Thermo*>(L.thermo); }
-Thermo& ensure(SfLammps& L)
-{
-  if (!L.thermo) {
-    L.thermo = new Thermo();
-    L.thermo_delete = [](void* p) { delete static_cast<Thermo*>(p); };
-  }
-  return *get(L);
-}
+Thermo* get(const SfLammps& L) { return L.thermo.get<Thermo>(); }
+Thermo& ensure(SfLammps& L) { return L.thermo.ensure<Thermo>(); }
 
 // only rank 0 writes (a host that decomposed through sf_slab_init keeps world_rank 0 on every rank: its engine rank counts)
 bool writer(const SfLammps& L) { return L.world_rank == 0 && L.eng.rank() == 0; }
@@ -368,18 +359,7 @@ void check_compute_cols(const SfLammps& L, const std::vector<ComputeCol>& cols)
   if (cols.empty()) return;
   if (L.world_size > 1 || L.decomposed || L.eng.nranks() > 1 || L.eng.decomposed())
     fail("thermo_style custom: c_ columns on one rank only (no decomposed domain)");
-  for (const ComputeCol& c : cols) {
-    bool vec = false;
-    const int n = global_compute_nvalues(L, c.id, &vec);
-    if (n == 0) {
-      if (atom_compute_ncols(L, c.id) > 0 || pair_local_exists(L, c.id) || rdf_array_rows(L, c.id) > 0)
-        fail(c.index == 0 ? "Thermo compute does not compute scalar" : "Thermo compute does not compute vector");
-      fail("Could not find thermo custom compute ID: %s", c.id.c_str());
-    }
-    if (c.index == 0 && vec) fail("Thermo compute does not compute scalar");
-    if (c.index > 0 && !vec) fail("Thermo compute does not compute vector");
-    if (c.index > n) fail("Thermo compute vector is accessed out-of-range");
-  }
+  for (const ComputeCol& c : cols) fail_if(check_thermo(compute_shape(L, c.id), c.index, c.id));
 }
 
 void line(SfLammps& L, Thermo& T)
@@ -430,10 +410,8 @@ void line(SfLammps& L, Thermo& T)
     for (size_t j = 0; j < T.ccols.size(); j++) {
       ComputeCol& cc = T.ccols[j];
       if (j == 0 || T.ccols[j - 1].id != cc.id) global_values_host(L, cc.id, &vals);
-      bool vec = false, ext = false;
-      global_compute_nvalues(L, cc.id, &vec, &ext);
       cc.value = vals[cc.index > 0 ? cc.index - 1 : 0];
-      if (ext && T.norm() && N > 0.0) cc.value /= N;
+      if (global_compute_extensive(L, cc.id) && T.norm() && N > 0.0) cc.value /= N;
     }
   }
   T.have_line = true;
