@@ -208,12 +208,21 @@ long long sf_lammps_compute_array(void *ptr, const char *id, long long max, doub
  * duplicates (the group atoms in a pair's itype range, jtype range and both).  Returns npairs x Nbin, or -1; with max smaller
  * than that nothing is evaluated or written */
 long long sf_lammps_rdf_counts(void *ptr, const char *id, long long max, long long *counts, long long *per_pair, int *npairs);
-/* cutoff grids built, kernel launches made and device-to-host copies made for compute rdf and coord/atom so far (all 0 for
- * a run that evaluates neither) */
+/* cutoff grids built, kernel launches made and device-to-host copies made for compute rdf, coord/atom and cluster/atom so
+ * far (all 0 for a run that evaluates none of them; cluster/atom copies 4 bytes per verify round) */
 int sf_lammps_nbr_launches(void *ptr, long long *grid_builds, long long *launches, long long *host_copies);
-/* measurement (tools/nbr_cost.py): GPU ms from HIP events of one fresh grid build and of one walk of compute `id` (rdf or
- * coord/atom) now */
+/* measurement (tools/nbr_cost.py, tools/cluster_cost.py): GPU ms from HIP events of one fresh grid build and of one walk of
+ * compute `id` (rdf, coord/atom or cluster/atom: there the walk is everything after the grid, the verify rounds and the
+ * waits for their flag included) now */
 int sf_lammps_nbr_cost(void *ptr, const char *id, double *grid_ms, double *walk_ms);
+/* flocs (`compute ID group cluster/atom CUT [surface no|yes] [size no|yes]`, a per-atom compute behind
+ * sf_lammps_compute_atom: the smallest tag of the atom's connected component, two atoms of the group linked when
+ * rsq < CUT^2, or with surface yes when rsq < ((ri + rj) + CUT)^2; with size yes a second column, the atoms of the
+ * component; and `compute ID group cluster/stats CID`, a global vector behind sf_lammps_compute_global: the distinct
+ * cluster IDs, the most atoms under one ID, the atoms with an ID).  Union-find on the grid of the cutoff, checked by a
+ * verify launch that is repeated until it finds nothing to hook: *rounds the verify rounds of the last evaluation of compute
+ * cluster/atom `id` (1 unless a round had to hook; 0 before the first evaluation).  Returns 0, or -1 (sf_last_error) */
+int sf_lammps_cluster_rounds(void *ptr, const char *id, int *rounds);
 /* unwrapped coordinates (the attributes xu yu zu ix iy iz of `compute property/atom`, `compute ID group displace/atom`,
  * `compute ID group com`): the engine counts, per tag, how many box
  * lengths the periodic wrap has taken an atom back by.  out[3 * nlocal]: ix iy iz of the owned atoms in the atom order

@@ -1,5 +1,5 @@
 // sf_compute_atom.h -- the per-atom computes `compute ID group stress/atom | contact/atom | ke/atom | erotate/sphere/atom |
-// property/atom` (sf_compute_atom.hip): one value (stress/atom: six; property/atom: one per attribute) per owned atom, evaluated on the GPU from the state at the moment of
+// property/atom | displace/atom | coord/atom | cluster/atom` (sf_compute_atom.hip): one value (stress/atom: six; property/atom: one per attribute) per owned atom, evaluated on the GPU from the state at the moment of
 // the output, behind the `c_ID` / `c_ID[k]` columns of `dump custom` (sf_dump.hip) and sf_lammps_compute_atom.  They share
 // the ID space of the other computes: sf_compute_ids.h owns `compute` / `uncompute`, and these styles (chunk/atom of
 // sf_chunk.hip among them, forwarded) plug in there as atom_compute_kind().
@@ -7,10 +7,9 @@
 #include <string>
 #include <vector>
 
-#include "sf_nbr_parse.h"
+#include "sf_nbr.h"
 
 namespace sf {
-struct SfLammps;
 
 // The values of compute `id` on the state as it stands, field-major on the device: column c of atom index i at
 // [c * nlocal + i]; atoms outside the compute's group hold 0.  Evaluated once per step however many dumps and queries
@@ -22,6 +21,10 @@ double atom_compute_cost(SfLammps& L, const std::string& id);
 // compute coord/atom `id`: its group bit, cutoff and type ranges (sf_lammps_nbr_cost times its grid and walk); false: no
 // compute coord/atom has this ID
 bool atom_compute_coord_spec(const SfLammps& L, const std::string& id, int* groupbit, double* rc, std::vector<TypeRange>* ranges);
+// compute cluster/atom `id`: its group bit and spec, and what it keeps between evaluations (the verify rounds of the last one
+// among it; sf_lammps_nbr_cost times its grid and walk, compute cluster/stats asks whether CID is one); nullptr: no compute
+// cluster/atom has this ID
+ClusterWork* atom_compute_cluster_spec(const SfLammps& L, const std::string& id, int* groupbit, ClusterSpec* spec);
 // compute displace/atom: is there one, and lammps_create_particle has made atoms with the tags d_tags[0 .. np) (device) --
 // where they are now is their reference (displace_created of sf_displace.hip calls both)
 bool atom_compute_tracks_created(const SfLammps& L);

@@ -17,12 +17,17 @@
 //   compute ID group coord/atom cutoff Rc [typerange ...]   the atoms j != i (of any group) with rsq < Rc^2, per type range:
 //                                          a walk of a grid of that cutoff on the positions as they stand (sf_nbr.hip;
 //                                          DESIGN.md 20), not of the pair list.  One range a vector, several an array
+//   compute ID group cluster/atom CUT [surface no|yes] [size no|yes]   the smallest tag of the atom's connected component,
+//                                          two group atoms linked when rsq < CUT^2 ([3P] ComputeClusterAtom); [own] surface
+//                                          yes: when rsq < ((ri + rj) + CUT)^2, the reach test of fix cohesive; [own] size yes:
+//                                          a second column, the atoms of the component.  Union-find on the same grid
+//                                          (sf_nbr.hip): several launches and one 4-byte copy per verify round
 // The group selects the atoms that get a value; atoms outside it read 0.  Like compute pair/local (sf_contacts.hip) a
 // value is evaluated from the state AT THE MOMENT OF THE OUTPUT -- the x v omega a dump custom frame shows, the shear
 // history sf_dem_get_history returns -- with shearupdate = false, and nothing is stored back.  (LAMMPS tallies vatom inside
 // the step's force evaluation, with the half-step velocities; at `run 0` the two coincide.)
 //
-// One launch per evaluation, one lane per owned atom, field-major stores val[c][i]; no atomics, no LDS, no
+// One launch per evaluation (coord/atom and cluster/atom: those of sf_nbr.hip), one lane per owned atom, field-major stores val[c][i]; no atomics, no LDS, no
 // floating-point reduction across lanes: the same state gives the same bits.  An evaluation is kept with the step it was
 // made at and shared by every dump and query of that step.
 #include <algorithm>
@@ -256,10 +261,10 @@ __global__ __launch_bounds__(256) void k_atom_displace(const double4* xr, const 
 
 // ---- host side ----
 
-enum Kind { K_STRESS, K_CONTACT, K_KE, K_EROTATE, K_PROPERTY, K_DISPLACE, K_COORD };
-constexpr int kNumKinds = 7;
+enum Kind { K_STRESS, K_CONTACT, K_KE, K_EROTATE, K_PROPERTY, K_DISPLACE, K_COORD, K_CLUSTER };
+constexpr int kNumKinds = 8;
 const char* const kStyleName[kNumKinds] = {"stress/atom", "contact/atom", "ke/atom", "erotate/sphere/atom", "property/atom",
-                                           "displace/atom", "coord/atom"};
+                                           "displace/atom", "coord/atom", "cluster/atom"};
 
 struct AtomCompute {
   std::string id;
@@ -269,11 +274,14 @@ struct AtomCompute {
   std::vector<int> attrs;   // K_PROPERTY
   RefTable ref;             // K_DISPLACE: the reference positions, by tag
   CoordSpec coord;          // K_COORD: the cutoff and the type ranges
+  ClusterSpec cluster;      // K_CLUSTER: the cutoff, the link rule and whether the size column exists
+  ClusterWork cluster_work; // K_CLUSTER: the union-find scratch, kept like val, and the verify rounds of the last evaluation
   DeviceScratch val;
   StateStamp made;   // what the buffer was made at
   int ncols() const
   {
     if (kind == K_COORD) return (int)coord.ranges.size();
+    if (kind == K_CLUSTER) return cluster.size ? 2 : 1;
     return kind == K_STRESS ? 6 : (kind == K_PROPERTY ? (int)attrs.size() : (kind == K_DISPLACE ? 4 : 1));
   }
   bool needs_image() const
@@ -330,6 +338,8 @@ void evaluate(SfLammps& L, AtomSet& T, AtomCompute& c)
   double* val = static_cast<double*>(c.val.get(sizeof(double) * (size_t)c.ncols() * (size_t)std::max(n, 1), st));
   if (c.kind == K_COORD) {   // (the grid and the walk are launches of sf_nbr.hip, counted there)
     nbr_coord_atom(L, "compute coord/atom", c.groupbit, c.coord.rc, c.coord.ranges, val);
+  } else if (c.kind == K_CLUSTER) {
+    nbr_cluster_atom(L, "compute cluster/atom", c.groupbit, c.cluster, c.cluster_work, val);
   } else if (n > 0) {
     const unsigned nb = (unsigned)div_up(n, 256);
     if (c.kind == K_KE || c.kind == K_EROTATE) {
@@ -377,6 +387,7 @@ void evaluate(SfLammps& L, AtomSet& T, AtomCompute& c)
 bool is_style(const std::string& style)
 {
   if (style == "chunk/atom") return true;   // (the fifth per-atom style: sf_chunk.hip holds it, the functions below forward)
+  if (!cluster_unsupported_style(style).empty()) return true;   // (refused by name in define)
   for (const char* s : kStyleName)
     if (style == s) return true;
   return false;
@@ -388,6 +399,7 @@ void define(SfLammps& L, const std::vector<std::string>& w)
     chunk_compute_define(L, w);
     return;
   }
+  fail_if(cluster_unsupported_style(w[3]));
   auto c = std::make_unique<AtomCompute>();
   c->id = w[1];
   c->groupbit = L.eng.group_bit(w[2]);
@@ -405,6 +417,8 @@ void define(SfLammps& L, const std::vector<std::string>& w)
   } else if (c->kind == K_COORD) {
     const std::string err = parse_coord_atom(w, &c->coord);
     if (!err.empty()) fail("%s", err.c_str());
+  } else if (c->kind == K_CLUSTER) {
+    fail_if(parse_cluster_atom(w, &c->cluster));
   } else if (w.size() != 4)
     fail("Illegal compute %s command", w[3].c_str());
   refuse_unsupported(L, c->kind);
@@ -470,6 +484,16 @@ bool atom_compute_coord_spec(const SfLammps& L, const std::string& id, int* grou
   *rc = c->coord.rc;
   *ranges = c->coord.ranges;
   return true;
+}
+
+ClusterWork* atom_compute_cluster_spec(const SfLammps& L, const std::string& id, int* groupbit, ClusterSpec* spec)
+{
+  AtomSet* T = set_of(L);
+  AtomCompute* c = T ? T->find(id) : nullptr;
+  if (!c || c->kind != K_CLUSTER) return nullptr;
+  if (groupbit) *groupbit = c->groupbit;
+  if (spec) *spec = c->cluster;
+  return &c->cluster_work;
 }
 
 bool atom_compute_tracks_created(const SfLammps& L)

@@ -72,7 +72,8 @@ bool compute_command(SfLammps& L, const std::vector<std::string>& w)
     fail("Invalid compute style %s (this engine has compute pair/local, also under the name gran/local, the per-atom "
          "computes stress/atom, contact/atom, ke/atom, erotate/sphere/atom, property/atom and chunk/atom, and the global "
          "computes reduce, ke and erotate/sphere; on unwrapped coordinates the per-atom compute displace/atom and the global "
-         "compute com; on a grid of the user's cutoff the global array rdf and the per-atom compute coord/atom)", style.c_str());
+         "compute com; on a grid of the user's cutoff the global array rdf and the per-atom computes coord/atom and cluster/atom, and "
+         "the global compute cluster/stats)", style.c_str());
   (void)L.eng.group_bit(w[2]);   // (the group must exist, before the ID is looked at)
   if (compute_shape(L, w[1]).kind != CK_NONE) fail("Reuse of compute ID");
   owner->define(L, w);

@@ -6,6 +6,9 @@
 //   compute ID group com                      sum m unmap(x) / sum m over the group ([3P] Group::xcm), three values
 //                                             (a mean squared displacement is compute reduce avesq
 //                                             over the columns of a compute displace/atom)
+//   compute ID group cluster/stats CID        [own] over the group atoms whose value of compute cluster/atom CID is not 0: the
+//                                             distinct cluster IDs, the most atoms under one ID, the atoms; three values
+//                                             
 //   fix ID group ave/time Nevery Nrepeat Nfreq c_ID c_ID[k] ... [ave one|running|window M] [start N] [file F] [overwrite]
 //       [format S] [title1 S] [title2 S]       time averages of global values, one line per Nfreq steps
 //       ... c_ID[k] ... mode vector [title3 S]   the columns of global arrays of one row count (compute rdf, sf_nbr.hip): a
@@ -26,6 +29,9 @@
 //                    counts by tag; the sums stay in registers, go through the same wave64 tree and LDS step into one partial row per block, and the block
 //                    that arrives last (an integer ticket behind an agent-scope release) folds the rows in row order and
 //                    stores the values
+//   k_cluster_rows, k_cluster_stats   compute cluster/stats: an integer counter per tag takes one integer atomic add per
+//                    atom; then ONE launch counts the rows that are not zero (ballots), their maximum and their sum through the
+//                    same tree and the same last-block fold.  Integers only
 // More than 16 columns take more launches; atom columns and row columns have different element counts and go in separate
 // launches.  No floating-point atomics, no scratch: the same state gives the same bits, and which thread adds which element
 // does not depend on the other columns of the launch.  Nothing is copied to the host before an output step, a thermo line
@@ -276,11 +282,72 @@ __global__ __launch_bounds__(kGBlock) void k_global_unwrapped(UArgs A, long long
   }
 }
 
+// ---- compute cluster/stats ----
+
+// cnt[t]: the group atoms whose cluster ID (column 1 of a compute cluster/atom: a tag, or 0) is t; rows: the largest tag + 1
+__global__ __launch_bounds__(kGBlock) void k_cluster_rows(const double* cid, const int* mask, int groupbit, int n, int rows,
+                                                          int* cnt)
+{
+  const int i = blockIdx.x * kGBlock + threadIdx.x;
+  if (i >= n || !(mask[i] & groupbit)) return;
+  const int t = (int)cid[i];
+  if (t > 0 && t < rows) atomicAdd(&cnt[t], 1);
+}
+
+constexpr int kSCols = 3;   // rows that are not zero, the largest row, the sum of the rows
+// The hand-over of k_global_unwrapped: one partial row per block, an integer ticket behind an agent-scope release, the fold in
+// the block that arrives last.  Every value is an integer below 2^31 carried in a double: exact in any order
+__global__ __launch_bounds__(kGBlock) void k_cluster_stats(const int* cnt, int rows, double* partial, unsigned* ticket, double* out)
+{
+  __shared__ int last;
+  __shared__ double folded[kSCols];
+  double acc[kSCols] = {0.0, 0.0, 0.0};
+  const int lane = threadIdx.x & 63;
+  const long long stride = (long long)gridDim.x * kGBlock;
+  // (the trip count is the same for every lane of a wave: the ballot sees the whole wave, and lane 0 adds its count)
+  for (long long base = (long long)blockIdx.x * kGBlock + (threadIdx.x - lane); base < rows; base += stride) {
+    const long long r = base + lane;
+    const int c = r < rows ? cnt[r] : 0;
+    const int nz = __popcll(__ballot(c > 0));
+    if (lane == 0) acc[0] += (double)nz;
+    acc[1] = fmax(acc[1], (double)c);
+    acc[2] += (double)c;
+  }
+  auto comb = [](int q, double a, double b) { return q == 1 ? fmax(a, b) : a + b; };
+  block_reduce_store<kGBlock, kSCols>(acc, partial + (size_t)kSCols * blockIdx.x, kSCols, comb);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned drawn = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last = drawn == gridDim.x - 1 ? 1 : 0;
+    if (last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+  }
+  __syncthreads();
+  if (!last) return;
+  double v[kSCols] = {0.0, 0.0, 0.0};
+  for (int b = threadIdx.x; b < (int)gridDim.x; b += kGBlock) {
+    v[0] += partial[(size_t)kSCols * b];
+    v[1] = fmax(v[1], partial[(size_t)kSCols * b + 1]);
+    v[2] += partial[(size_t)kSCols * b + 2];
+  }
+  block_reduce_store<kGBlock, kSCols>(v, folded, kSCols, comb);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int q = 0; q < kSCols; q++) out[q] = folded[q];
+    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 // ---- host side ----
 
-enum GKind { G_REDUCE, G_KE, G_EROTATE, G_COM };
-constexpr int kNumGKinds = 4;
-const char* const kStyleName[kNumGKinds] = {"reduce", "ke", "erotate/sphere", "com"};
+enum GKind { G_REDUCE, G_KE, G_EROTATE, G_COM, G_CLUSTER };
+constexpr int kNumGKinds = 5;
+const char* const kStyleName[kNumGKinds] = {"reduce", "ke", "erotate/sphere", "com", "cluster/stats"};
 
 struct GlobalCompute {
   std::string id;
@@ -290,9 +357,12 @@ struct GlobalCompute {
   int nvalues = 1;
   int slot = -1;   // in the pool
   StateStamp made;   // what the values were made at
+  std::string cid;           // G_CLUSTER: the compute cluster/atom it reads
+  DeviceScratch tag_rows;    // G_CLUSTER: the integer counter per tag
   bool unwrapped() const { return kind == G_COM; }
-  bool is_vector() const { return unwrapped() || (kind == G_REDUCE && S.inputs.size() > 1); }
-  bool extensive() const { return !unwrapped() && (kind != G_REDUCE || S.mode == GM_SUM || S.mode == GM_SUMSQ); }
+  bool own_launches() const { return kind == G_COM || kind == G_CLUSTER; }   // not a column of k_global_gather
+  bool is_vector() const { return own_launches() || (kind == G_REDUCE && S.inputs.size() > 1); }
+  bool extensive() const { return !own_launches() && (kind != G_REDUCE || S.mode == GM_SUM || S.mode == GM_SUMSQ); }
 };
 
 struct AveTimeFix : AveFixState {
@@ -495,6 +565,37 @@ void evaluate_unwrapped(SfLammps& L, GlobalSet& G, GlobalCompute& c)
   G.launches++;
 }
 
+// CID of a compute cluster/stats: checked at the compute line and again at every evaluation (the compute may have been removed
+// or defined anew as something else)
+void check_cluster_id(const SfLammps& L, const std::string& cid)
+{
+  if (compute_shape(L, cid).kind == CK_NONE) fail("compute cluster/stats: Could not find compute ID %s", cid.c_str());
+  if (!atom_compute_cluster_spec(L, cid, nullptr, nullptr))
+    fail("compute cluster/stats: compute %s is not a compute cluster/atom", cid.c_str());
+}
+
+// compute cluster/stats: the counter per tag is zeroed, takes the atoms, and is reduced by one launch
+void evaluate_cluster_stats(SfLammps& L, GlobalSet& G, GlobalCompute& c)
+{
+  check_cluster_id(L, c.cid);
+  DemEngine& e = L.eng;
+  hipStream_t st = e.stream();
+  const int n = e.nlocal();
+  int nc = 0;
+  const double* cid = atom_compute_values(L, c.cid, &nc);   // (once per step however many ask; column 1 comes first)
+  const int rows = e.max_tag() + 1;
+  int* cnt = static_cast<int*>(c.tag_rows.get(sizeof(int) * (size_t)rows, st));
+  SF_HIP(hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)rows, st));
+  if (n > 0) {
+    k_cluster_rows<<<div_up(n, kGBlock), kGBlock, 0, st>>>(cid, e.d_mask(), c.groupbit, n, rows, cnt);
+    G.launches++;
+  }
+  const int nb = std::max(1, std::min(kGMaxBlocks, div_up(rows, kGBlock)));
+  k_cluster_stats<<<nb, kGBlock, 0, st>>>(cnt, rows, G.partial, G.ticket, G.pool + c.slot);
+  SF_HIP(hipGetLastError());
+  G.launches++;
+}
+
 // Every compute of `want` that is stale is evaluated, once; `accs`: the additions of the fix samples due now, carried by
 // the fold launches of the values they name (or by k_global_acc where the value was evaluated at this step before)
 void evaluate(SfLammps& L, GlobalSet& G, const std::vector<GlobalCompute*>& want, const std::vector<AccReq>& accs)
@@ -516,8 +617,9 @@ void evaluate(SfLammps& L, GlobalSet& G, const std::vector<GlobalCompute*>& want
   for (const AccReq& a : accs)
     if (std::find(stale.begin(), stale.end(), a.c) == stale.end()) late.push_back({G.pool + a.c->slot + a.value, a.dst});
   for (GlobalCompute* c : stale) {
-    if (c->unwrapped()) {   // (launches of their own; the samples of the fixes are added behind them)
-      evaluate_unwrapped(L, G, *c);
+    if (c->own_launches()) {   // (the samples of the fixes are added behind them)
+      if (c->unwrapped()) evaluate_unwrapped(L, G, *c);
+      else evaluate_cluster_stats(L, G, *c);
       for (const AccReq& a : accs)
         if (a.c == c) late.push_back({G.pool + c->slot + a.value, a.dst});
       continue;
@@ -731,6 +833,10 @@ void define(SfLammps& L, const std::vector<std::string>& w)
     c->nvalues = (int)c->S.inputs.size();
   } else if (c->kind == G_COM) {
     fail_if(parse_com(w));
+    c->nvalues = 3;
+  } else if (c->kind == G_CLUSTER) {
+    fail_if(parse_cluster_stats(w, &c->cid));
+    check_cluster_id(L, c->cid);
     c->nvalues = 3;
   } else if (w.size() != 4)
     fail("Illegal compute %s command", w[3].c_str());

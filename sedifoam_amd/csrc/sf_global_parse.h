@@ -71,6 +71,18 @@ inline std::string parse_reduce(const std::vector<std::string>& w, ReduceSpec* o
   return std::string();
 }
 
+// ---- compute cluster/stats [own] ----
+
+// w = compute ID group cluster/stats CID, CID the ID of a compute cluster/atom
+inline std::string parse_cluster_stats(const std::vector<std::string>& w, std::string* cid)
+{
+  if (w.size() != 5 || w[4].empty()) return "Illegal compute cluster/stats command";
+  if (w[4].compare(0, 2, "c_") == 0)
+    return "compute cluster/stats: give the ID of the cluster/atom compute itself (" + w[4].substr(2) + ", not " + w[4] + ")";
+  *cid = w[4];
+  return std::string();
+}
+
 // ---- compute property/atom ----
 
 enum PropAttr {

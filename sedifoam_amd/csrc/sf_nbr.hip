@@ -21,6 +21,17 @@
 //   k_rdf_norm    one lane per pair: g(r) and ncoord, operation by operation in the order of the rule
 //   k_nbr_coord   counts in registers, stored per atom
 // Every tally is an integer, so the bits do not depend on the order of the additions; no floating-point atomics.
+//
+// On the same grid, `compute ID group cluster/atom CUT [surface no|yes] [size no|yes]` ([3P] ComputeClusterAtom; DESIGN.md
+// section 21; sf_compute_atom.hip registers it): the connected components of "linked" as a union-find over the places of the
+// cell order, one lane per place.
+//   k_cl_init, k_cl_pack_radius   parent[p] = p for the group, -1 for the others; the radii in cell order (surface yes only)
+//   k_cl_edges<false>             the hook launch: every linked pair, from its higher place, unites its two trees
+//   k_cl_compress                 parent[p] = the root above p as the launch before left it
+//   k_cl_edges<true>              the verify launch: the same walk, writing nothing unless a pair is still apart; then it
+//                                 hooks it and raises a flag, and the host repeats compress + verify (at most 64 rounds)
+//   k_cl_tally, k_cl_store        integer atomics per root (smallest tag, count), then the per-atom values
+// What is and is not assumed about memory inside a launch stands above the kernels.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -112,10 +123,10 @@ __device__ __forceinline__ double nbr_delta(const NbrGridDev& G, int a, double x
   return d;
 }
 
-// f(j, rsq) for every place j != p of the cell (cx, cy, cz) and of the adjacent cells, each cell once
+// f(j, record of j, rsq) for every place j != p of the cell (cx, cy, cz) and of the adjacent cells, each cell once
 template <class F>
-__device__ __forceinline__ void nbr_walk(const NbrGridDev& G, const double4* pos, const int* start, int p, const double4& me,
-                                         int cx, int cy, int cz, F&& f)
+__device__ __forceinline__ void nbr_walk_places(const NbrGridDev& G, const double4* pos, const int* start, int p,
+                                                const double4& me, int cx, int cy, int cz, F&& f)
 {
   for (int oz = 0; oz < G.noff[2]; oz++) {
     int z = cz + G.off0[2] + oz;
@@ -136,11 +147,19 @@ __device__ __forceinline__ void nbr_walk(const NbrGridDev& G, const double4* pos
           const double4 o = pos[j];
           const double dx = nbr_delta(G, 0, o.x, me.x), dy = nbr_delta(G, 1, o.y, me.y), dz = nbr_delta(G, 2, o.z, me.z);
           const double rsq = (dx * dx + dy * dy) + dz * dz;
-          f(o, rsq);
+          f(j, o, rsq);
         }
       }
     }
   }
+}
+
+// ... for the walks that do not ask which place it is: f(record of j, rsq)
+template <class F>
+__device__ __forceinline__ void nbr_walk(const NbrGridDev& G, const double4* pos, const int* start, int p, const double4& me,
+                                         int cx, int cy, int cz, F&& f)
+{
+  nbr_walk_places(G, pos, start, p, me, cx, cy, cz, [&](int, const double4& o, double rsq) { f(o, rsq); });
 }
 
 struct RdfArgs {
@@ -266,6 +285,154 @@ __global__ __launch_bounds__(kNBlock) void k_nbr_coord(NbrGridDev G, const doubl
     if (k < A.nr) val[(size_t)k * (size_t)n + i] = (double)cnt[k];
 }
 
+// ---- compute cluster/atom: connected components over the places of the cell order ----
+//
+// parent[p] is a place of the same component with parent[p] <= p, or -1 for a place outside the group, which is never read as a
+// neighbour and never hooked.  What may be assumed about memory inside one launch: NOTHING about plain stores of other
+// workgroups (the L2s of the XCDs are not coherent and a CU's L1 is never refreshed).  So inside a launch `parent` is read and
+// written with agent-scope integer atomics alone, as k_nbr_keys does with `count`, and everything else (the records, the radii,
+// the flag's zero, mintag, cnt, val) is handed over at kernel boundaries.  And no result rests even on an atomic load being
+// fresh: a value of parent[q] that is out of date is an OLDER ANCESTOR of q in the same tree (an entry only ever moves from q
+// to an ancestor of q: a root is hooked once, under a smaller place, by a compare-and-swap that fails when it is no root any
+// more; halving and compressing replace a parent by a grandparent or the root), so whatever a load returns, a root-finding
+// loop walks a strictly decreasing chain inside q's tree and ends after at most n steps, and two places found under one place
+// ARE in one tree.  That the hooks are complete is not taken on trust either: the verify launch reads only what earlier
+// launches wrote unless it hooks something itself, and then it raises the flag and the host runs it again.
+struct ClusterArgs {
+  int groupbit, surface;
+  double cut, cutsq;
+};
+
+// The link rule.  Bit-symmetric in (i, j), which the walk relies on when it takes every edge from its higher place alone:
+// d = xj - xi and xi - xj are exact negations of each other, the two branches of the minimum image mirror each other, so rsq
+// has the same bits from both ends; ri + rj is commutative.  surface: [own] the reach test of fix cohesive with cut for smax,
+// each operation rounded once
+__device__ __forceinline__ bool cl_linked(const ClusterArgs& A, double rsq, double ri, double rj)
+{
+  if (A.surface) {
+    const double s = (ri + rj) + A.cut;
+    return rsq < s * s;
+  }
+  return rsq < A.cutsq;
+}
+
+__device__ __forceinline__ int cl_load(const int* parent, int q)
+{
+  return __hip_atomic_load(parent + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the root above q as far as this lane can see: parent[r] < r on every step, so at most q + 1 of them.  HALVE: an entry on
+// the way is lowered to its grandparent (an atomic minimum: the entry never rises, and a root is left alone)
+template <bool HALVE>
+__device__ __forceinline__ int cl_find(int* parent, int q)
+{
+  for (;;) {
+    const int r = cl_load(parent, q);
+    if (r == q) return q;
+    const int g = cl_load(parent, r);
+    if (g == r) return r;
+    if (HALVE) atomicMin(&parent[q], g);
+    q = g;
+  }
+}
+
+// the trees of a and b become one; true where this lane hooked a root.  A root `hi` goes under the smaller place `lo` (a root
+// or not: lo < hi keeps parent[q] <= q) only while it still is a root; where another lane was first, its new parent `old` is
+// an ancestor of hi below hi, and the loop goes on with (old, lo): max(a, b) falls with every turn
+template <bool HALVE>
+__device__ __forceinline__ bool cl_unite(int* parent, int a, int b)
+{
+  for (;;) {
+    a = cl_find<HALVE>(parent, a);
+    b = cl_find<HALVE>(parent, b);
+    if (a == b) return false;
+    const int hi = max(a, b), lo = min(a, b);
+    const int old = atomicCAS(&parent[hi], hi, lo);
+    if (old == hi) return true;
+    a = old;
+    b = lo;
+  }
+}
+
+// mintag and cnt are per place and used at the roots
+__global__ __launch_bounds__(kNBlock) void k_cl_init(const double4* pos, int n, int groupbit, int* parent, int* mintag, int* cnt)
+{
+  const int p = blockIdx.x * kNBlock + threadIdx.x;
+  if (p >= n) return;
+  parent[p] = (nbr_mask(pos[p]) & groupbit) ? p : -1;
+  mintag[p] = INT_MAX;
+  cnt[p] = 0;
+}
+
+// surface yes: the radii in cell order, next to the 32-byte records that rdf and coord/atom read
+__global__ __launch_bounds__(kNBlock) void k_cl_pack_radius(const double4* xr, const int* idx, int n, double* rad)
+{
+  const int p = blockIdx.x * kNBlock + threadIdx.x;
+  if (p < n) rad[p] = xr[idx[p]].w;
+}
+
+// One lane per place p of the group: every linked neighbour at a place j < p (each edge once, from its higher end; the record
+// and the radius of j are one broadcast line each for the lanes of a cell).  VERIFY = false, the hook launch: the two trees
+// are united.  VERIFY = true, a launch of its own behind a compress: the same, without halving, so that a launch in which
+// every pair is found under one root has written nothing and has read only what earlier launches wrote; a pair that is not
+// is hooked and raises the flag
+template <bool VERIFY>
+__global__ __launch_bounds__(kNBlock) void k_cl_edges(NbrGridDev G, const double4* pos, const int* start, const double* rad, int n,
+                                                      ClusterArgs A, int* parent, int* flag)
+{
+  const int p = blockIdx.x * kNBlock + threadIdx.x;
+  if (p >= n) return;
+  const double4 me = pos[p];
+  if (!(nbr_mask(me) & A.groupbit)) return;
+  const double ri = A.surface ? rad[p] : 0.0;
+  int cx, cy, cz;
+  nbr_cell(G, me.x, me.y, me.z, &cx, &cy, &cz);
+  bool raised = false;
+  nbr_walk_places(G, pos, start, p, me, cx, cy, cz, [&](int j, const double4& o, double rsq) {
+    if (j > p || !(nbr_mask(o) & A.groupbit)) return;
+    const double rj = A.surface ? rad[j] : 0.0;
+    if (!cl_linked(A, rsq, ri, rj)) return;
+    if (cl_unite<!VERIFY>(parent, p, j)) raised = true;
+  });
+  if (VERIFY && raised) atomicOr(flag, 1);
+}
+
+// parent[p] becomes the root above p in the array as the launch before left it: no root moves in this launch, and an entry
+// another lane has stored already is that lane's root, which is this one's too.  Place 0 zeroes the flag of the verify launch
+// that follows (handed over by the kernel boundary)
+__global__ __launch_bounds__(kNBlock) void k_cl_compress(int* parent, int n, int* flag)
+{
+  const int p = blockIdx.x * kNBlock + threadIdx.x;
+  if (p >= n) return;
+  if (p == 0) *flag = 0;
+  const int q = cl_load(parent, p);
+  if (q < 0) return;
+  const int r = cl_find<false>(parent, q);
+  if (r != q) __hip_atomic_store(parent + p, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// behind a verify launch that raised nothing: parent[p] is the root.  Integer atomics: the order changes no bit
+__global__ __launch_bounds__(kNBlock) void k_cl_tally(const int* parent, const int* idx, const int* tag, int n, int size,
+                                                      int* mintag, int* cnt)
+{
+  const int p = blockIdx.x * kNBlock + threadIdx.x;
+  if (p >= n) return;
+  const int r = parent[p];
+  if (r < 0) return;
+  atomicMin(&mintag[r], tag[idx[p]]);
+  if (size) atomicAdd(&cnt[r], 1);
+}
+
+__global__ __launch_bounds__(kNBlock) void k_cl_store(const int* parent, const int* idx, int n, int size, const int* mintag,
+                                                      const int* cnt, double* val)
+{
+  const int p = blockIdx.x * kNBlock + threadIdx.x;
+  if (p >= n) return;
+  const int r = parent[p], i = idx[p];
+  val[i] = r < 0 ? 0.0 : (double)mintag[r];
+  if (size) val[(size_t)n + i] = r < 0 ? 0.0 : (double)cnt[r];
+}
+
 // ---- host side ----
 
 struct RawTmp {   // the scratch of the sort and scan wrappers of sf_sort.hip, which grow it themselves
@@ -282,8 +449,9 @@ struct NbrGrid {
   NbrGridDev D{};
   int ncells = 1;
   DeviceScratch key_in, idx_in, key_out, idx_out, count, start, pos;
+  DeviceScratch rad;   // the radii in cell order: made when a compute cluster/atom with surface yes asks, never otherwise
   RawTmp sort_tmp, scan_tmp;
-  StateStamp made;   // what it was made at
+  StateStamp made, rad_made;   // what it (and rad) was made at
 };
 
 struct RdfCompute {
@@ -400,6 +568,7 @@ void build_grid(SfLammps& L, NbrSet& T, NbrGrid& g, const NbrGridDev& D, int nce
   T.launches++;
   T.grid_builds++;
   g.made.set(e);
+  g.rad_made.clear();
 }
 
 // the grid of cutoff rc on the state as it stands: kept with the step, the rebuild count, the atom count and the cell
@@ -478,6 +647,58 @@ void coord_walk(SfLammps& L, NbrSet& T, const NbrGrid& g, const CoordArgs& A, do
   T.launches++;
 }
 
+constexpr int kClusterMaxRounds = 64;
+
+// init, hook, then compress + verify until a verify launch raises nothing (one 4-byte copy per round), tally, store
+void cluster_walk(SfLammps& L, NbrSet& T, NbrGrid& g, const char* who, int groupbit, const ClusterSpec& S, ClusterWork& W,
+                  double* val)
+{
+  DemEngine& e = L.eng;
+  hipStream_t st = e.stream();
+  const int n = e.nlocal();
+  W.rounds = 0;
+  if (n <= 0) return;
+  const size_t m = (size_t)n;
+  int* parent = static_cast<int*>(W.buf.get(sizeof(int) * (3 * m + 4), st));
+  int *mintag = parent + m, *cnt = mintag + m, *flag = cnt + m;
+  const unsigned nb = (unsigned)div_up(n, kNBlock);
+  const double4* pos = g.pos.as<double4>();
+  const int *start = g.start.as<int>(), *idx = g.idx_out.as<int>();
+  const double* rad = nullptr;
+  if (S.surface) {
+    double* r = static_cast<double*>(g.rad.get(sizeof(double) * m, st));
+    if (!g.rad_made.is_now(e)) {
+      k_cl_pack_radius<<<nb, kNBlock, 0, st>>>(e.d_xr(), idx, n, r);
+      SF_HIP(hipGetLastError());
+      T.launches++;
+      g.rad_made.set(e);
+    }
+    rad = r;
+  }
+  const ClusterArgs A{groupbit, S.surface ? 1 : 0, S.cut, S.cut * S.cut};
+  k_cl_init<<<nb, kNBlock, 0, st>>>(pos, n, groupbit, parent, mintag, cnt);
+  k_cl_edges<false><<<nb, kNBlock, 0, st>>>(g.D, pos, start, rad, n, A, parent, flag);
+  SF_HIP(hipGetLastError());
+  T.launches += 2;
+  for (;;) {
+    k_cl_compress<<<nb, kNBlock, 0, st>>>(parent, n, flag);
+    k_cl_edges<true><<<nb, kNBlock, 0, st>>>(g.D, pos, start, rad, n, A, parent, flag);
+    SF_HIP(hipGetLastError());
+    T.launches += 2;
+    int raised = 0;
+    SF_HIP(hipMemcpyAsync(&raised, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    SF_HIP(hipStreamSynchronize(st));
+    T.host_copies++;
+    W.rounds++;
+    if (!raised) break;
+    if (W.rounds >= kClusterMaxRounds) fail("%s: the components did not settle within %d verify rounds", who, W.rounds);
+  }
+  k_cl_tally<<<nb, kNBlock, 0, st>>>(parent, idx, e.d_tag(), n, S.size ? 1 : 0, mintag, cnt);
+  k_cl_store<<<nb, kNBlock, 0, st>>>(parent, idx, n, S.size ? 1 : 0, mintag, cnt, val);
+  SF_HIP(hipGetLastError());
+  T.launches += 2;
+}
+
 RdfCompute& rdf_of(SfLammps& L, const std::string& id)
 {
   NbrSet* T = set_of(L);
@@ -534,7 +755,7 @@ void invalidate(SfLammps& L)
 {
   if (NbrSet* T = set_of(L)) {
     for (auto& c : T->computes) c->made.clear();
-    for (auto& g : T->grids) g->made.clear();
+    for (auto& g : T->grids) g->made.clear(), g->rad_made.clear();
   }
 }
 
@@ -561,6 +782,20 @@ void nbr_coord_atom(SfLammps& L, const char* who, int groupbit, double rc, const
   NbrSet& T = ensure_set(L);
   const NbrGrid& g = grid_of(L, T, who, rc);
   coord_walk(L, T, g, coord_args(groupbit, rc, ranges), val);
+}
+
+double nbr_cluster_grid_cutoff(SfLammps& L, const ClusterSpec& S)
+{
+  // (the engine's largest radius, max_radius(): one rank here, so the local one is it)
+  return S.surface ? 2.0 * L.eng.local_max_radius() + S.cut : S.cut;
+}
+
+void nbr_cluster_atom(SfLammps& L, const char* who, int groupbit, const ClusterSpec& S, ClusterWork& W, double* val)
+{
+  nbr_refuse_unsupported(L, who);
+  NbrSet& T = ensure_set(L);
+  NbrGrid& g = grid_of(L, T, who, nbr_cluster_grid_cutoff(L, S));
+  cluster_walk(L, T, g, who, groupbit, S, W, val);
 }
 
 }  // namespace sf
@@ -627,7 +862,19 @@ int sf_lammps_nbr_launches(void* ptr, long long* grid_builds, long long* launche
   SF_API_END(0)
 }
 
-// GPU milliseconds from HIP events of one fresh grid build and one walk of compute `id` (rdf or coord/atom)
+// the verify rounds of the last evaluation of compute cluster/atom `id` (0: not evaluated yet, or no atoms)
+int sf_lammps_cluster_rounds(void* ptr, const char* id, int* rounds)
+{
+  SF_API_BEGIN
+  if (!id || !rounds) sf::fail("sf_lammps_cluster_rounds: null argument");
+  const sf::ClusterWork* W = sf::atom_compute_cluster_spec(*handle(ptr), id, nullptr, nullptr);
+  if (!W) sf::fail("Could not find compute cluster/atom ID %s", id);
+  *rounds = W->rounds;
+  SF_API_END(0)
+}
+
+// GPU milliseconds from HIP events of one fresh grid build and one walk of compute `id` (rdf, coord/atom or cluster/atom: its
+// walk is everything after the grid, the waits for the flag of the verify rounds included)
 int sf_lammps_nbr_cost(void* ptr, const char* id, double* grid_ms, double* walk_ms)
 {
   SF_API_BEGIN
@@ -635,12 +882,22 @@ int sf_lammps_nbr_cost(void* ptr, const char* id, double* grid_ms, double* walk_
   if (!id || !grid_ms || !walk_ms) sf::fail("sf_lammps_nbr_cost: null argument");
   hipStream_t st = L.eng.stream();
   sf::NbrSet& T = sf::ensure_set(L);
+  int cl_groupbit = 1;
+  sf::ClusterSpec cl;
   if (sf::RdfCompute* c = T.find(id)) {
     sf::nbr_refuse_unsupported(L, "compute rdf");
     sf::NbrGrid* g = nullptr;
     *grid_ms = sf::stream_ms(st, [&] { g = &sf::grid_of(L, T, "compute rdf", c->S.rc, true); });
     *walk_ms = sf::stream_ms(st, [&] { sf::rdf_walk(L, T, *c, *g); });
     c->made.set(L.eng);
+  } else if (sf::ClusterWork* W = sf::atom_compute_cluster_spec(L, id, &cl_groupbit, &cl)) {
+    const char* who = "compute cluster/atom";
+    sf::nbr_refuse_unsupported(L, who);
+    const size_t cells = (cl.size ? 2 : 1) * (size_t)std::max(L.eng.nlocal(), 1);
+    double* val = static_cast<double*>(T.cost_val.get(sizeof(double) * cells, st));   // (not in the time)
+    sf::NbrGrid* g = nullptr;
+    *grid_ms = sf::stream_ms(st, [&] { g = &sf::grid_of(L, T, who, sf::nbr_cluster_grid_cutoff(L, cl), true); });
+    *walk_ms = sf::stream_ms(st, [&] { sf::cluster_walk(L, T, *g, who, cl_groupbit, cl, *W, val); });   // (everything after the grid)
   } else {
     int groupbit = 1;
     double rc = 0.0;

@@ -1,5 +1,6 @@
-// sf_nbr_parse.h -- the words of `compute ID group rdf Nbin [itype jtype ...] cutoff Rc` and `compute ID group coord/atom
-// cutoff Rc [typerange ...]` ([3P] LAMMPS names: ComputeRDF::ComputeRDF, ComputeCoordAtom::ComputeCoordAtom, utils::bounds
+// sf_nbr_parse.h -- the words of `compute ID group rdf Nbin [itype jtype ...] cutoff Rc`, `compute ID group coord/atom
+// cutoff Rc [typerange ...]` and `compute ID group cluster/atom CUT [surface no|yes] [size no|yes]` ([3P] LAMMPS names:
+// ComputeRDF::ComputeRDF, ComputeCoordAtom::ComputeCoordAtom, ComputeClusterAtom::ComputeClusterAtom, utils::bounds
 // for a type range), on the host with nothing but the standard library, so that this code can be compiled into a stand-alone
 // program and run under the host sanitizers (tests/c_abi/nbr_parse_check.cpp; sf_chunk_parse.h is the precedent).  Every
 // parser returns an empty string, or the error text.
@@ -117,6 +118,44 @@ inline std::string parse_coord_atom(const std::vector<std::string>& w, CoordSpec
   }
   if (S.ranges.empty()) S.ranges.push_back(TypeRange());
   *out = S;
+  return std::string();
+}
+
+// ---- compute cluster/atom ([3P] LAMMPS name and rule: ComputeClusterAtom) ----
+
+struct ClusterSpec {
+  double cut = 0.0;
+  bool surface = false;   // [own] linked when rsq < ((ri + rj) + cut)^2: the reach test of fix cohesive
+  bool size = false;      // [own] a second column: the atoms of the atom's cluster
+};
+
+// w = compute ID group cluster/atom CUT [surface no|yes] [size no|yes]
+inline std::string parse_cluster_atom(const std::vector<std::string>& w, ClusterSpec* out)
+{
+  const std::string illegal = "Illegal compute cluster/atom command";
+  if (w.size() < 5) return illegal;
+  ClusterSpec S;
+  char* end = nullptr;
+  S.cut = w[4].empty() ? 0.0 : std::strtod(w[4].c_str(), &end);
+  if (w[4].empty() || end == w[4].c_str() || *end != '\0' || !std::isfinite(S.cut)) return illegal;
+  for (size_t k = 5; k < w.size(); k += 2) {
+    if (k + 1 >= w.size() || (w[k + 1] != "no" && w[k + 1] != "yes")) return illegal;
+    const bool yes = w[k + 1] == "yes";
+    if (w[k] == "surface") S.surface = yes;
+    else if (w[k] == "size") S.size = yes;
+    else return illegal;
+  }
+  // (a centre distance below zero links nothing and makes no grid; a gap of zero between surfaces is touching)
+  if (S.surface ? !(S.cut >= 0.0) : !(S.cut > 0.0)) return illegal;
+  *out = S;
+  return std::string();
+}
+
+// the bond-based siblings of cluster/atom, refused by name; empty: `style` is neither
+inline std::string cluster_unsupported_style(const std::string& style)
+{
+  if (style == "fragment/atom" || style == "aggregate/atom")
+    return "compute " + style + " is not supported (there are no bonds; cluster/atom is)";
   return std::string();
 }
 

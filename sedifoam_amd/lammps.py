@@ -168,7 +168,8 @@ class Lammps:
 
     def compute_atom(self, cid):
         """the values of the per-atom compute `cid` (stress/atom: [n, 6] in the order xx yy zz xy xz yz; contact/atom,
-        ke/atom, erotate/sphere/atom: [n]; property/atom: [n] for one attribute, [n, k] for several) now, sorted by tag like
+        ke/atom, erotate/sphere/atom: [n]; property/atom: [n] for one attribute, [n, k] for several; cluster/atom: [n] the
+        smallest tag of the atom's cluster, with size yes [n, 2] and the cluster's atom count behind it) now, sorted by tag like
         get_state(); atoms outside the compute's group read 0.
         What a `dump custom` column c_ID / c_ID[k] written at this moment holds.  Passive: the run goes on with the same bits"""
         cid = str(cid).encode()
@@ -222,8 +223,9 @@ class Lammps:
         return float(out[0]), float(out[1]), float(out[2])
 
     def compute_global(self, cid):
-        """the values of the global compute `cid` (compute reduce, ke, erotate/sphere) on the state as it stands: a float64
-        array, length 1 for a scalar; not normalised.  What a fix ave/time sample or a thermo column c_ID / c_ID[k] taken at
+        """the values of the global compute `cid` (compute reduce, ke, erotate/sphere, com; cluster/stats: the number of
+        clusters, the largest one's atoms, the atoms in clusters) on the state as it stands: a float64 array, length 1 for a
+        scalar; not normalised.  What a fix ave/time sample or a thermo column c_ID / c_ID[k] taken at
         this moment holds.  Passive: the run goes on with the same bits"""
         cid = str(cid).encode()
         vec = C.c_int()
@@ -279,16 +281,24 @@ class Lammps:
 
     def nbr_launches(self):
         """dict(grid_builds, launches, host_copies): cutoff grids built, kernel launches made and device-to-host copies made
-        for compute rdf and coord/atom so far"""
+        for compute rdf, coord/atom and cluster/atom so far (cluster/atom: one 4-byte copy per verify round)"""
         g = C.c_longlong(); n = C.c_longlong(); h = C.c_longlong()
         check(self.L.sf_lammps_nbr_launches(self.ptr, C.byref(g), C.byref(n), C.byref(h)))
         return dict(grid_builds=g.value, launches=n.value, host_copies=h.value)
 
     def nbr_cost(self, cid):
-        """GPU ms of (one fresh grid build, one walk) of compute rdf or coord/atom `cid` now"""
+        """GPU ms of (one fresh grid build, one walk) of compute rdf, coord/atom or cluster/atom `cid` now; the walk of a
+        cluster/atom is everything after the grid, the waits for the flag of its verify rounds included"""
         g = C.c_double(); w = C.c_double()
         check(self.L.sf_lammps_nbr_cost(self.ptr, str(cid).encode(), C.byref(g), C.byref(w)))
         return g.value, w.value
+
+    def cluster_rounds(self, cid):
+        """the verify rounds of the last evaluation of compute cluster/atom `cid`: 1 unless a verify launch had to hook a
+        pair the hook launch left apart; 0 before the first evaluation"""
+        r = C.c_int()
+        check(self.L.sf_lammps_cluster_rounds(self.ptr, str(cid).encode(), C.byref(r)))
+        return r.value
 
     def global_launches(self):
         """dict(launches, host_copies): kernel launches made for global computes and fix ave/time so far, and the
