@@ -223,6 +223,19 @@ int sf_lammps_nbr_cost(void *ptr, const char *id, double *grid_ms, double *walk_
  * verify launch that is repeated until it finds nothing to hook: *rounds the verify rounds of the last evaluation of compute
  * cluster/atom `id` (1 unless a round had to hook; 0 before the first evaluation).  Returns 0, or -1 (sf_last_error) */
 int sf_lammps_cluster_rounds(void *ptr, const char *id, int *rounds);
+/* chunks that a compute defines (`compute ID group chunk/atom c_CID | c_CID[k] [compress no|yes] [nchunk once|every]`: the
+ * chunk ID of a grain is the named per-atom column cast to int, 0 below 1 or outside the group; compress yes renumbers the
+ * distinct IDs 1 .. Nchunk in ascending order) and the per-chunk computes over them (`compute ID group property/chunk CID
+ * count [id]`, `com/chunk CID`, `vcm/chunk CID`, `gyration/chunk CID [tensor]`: global arrays of Nchunk rows behind
+ * sf_lammps_compute_array).  Returns Nchunk of chunk/atom compute `id` on the state as it stands, or -1 (sf_last_error); with
+ * Nchunk <= max, ids[Nchunk]: the original IDs under compress yes, 1 .. Nchunk otherwise.  *launches, *host_copies: the kernel
+ * launches (a sort or a scan counts as one) and device-to-host copies (4 bytes, Nchunk) that the evaluations of this compute and
+ * of the per-chunk computes over it have made so far; what a getter copies out is not among them */
+long long sf_lammps_chunk_info(void *ptr, const char *id, long long max, int *ids, long long *launches, long long *host_copies);
+/* measurement (tools/pchunk_cost.py): GPU ms from HIP events of one evaluation now of chunk/atom compute `id` (over c_CID) and
+ * of every per-chunk compute over it, the wait for the 4 bytes of Nchunk included; the compute behind c_CID is evaluated
+ * before the clock starts */
+int sf_lammps_chunk_cost(void *ptr, const char *id, double *ms);
 /* unwrapped coordinates (the attributes xu yu zu ix iy iz of `compute property/atom`, `compute ID group displace/atom`,
  * `compute ID group com`): the engine counts, per tag, how many box
  * lengths the periodic wrap has taken an atom back by.  out[3 * nlocal]: ix iy iz of the owned atoms in the atom order

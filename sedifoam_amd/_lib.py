@@ -144,6 +144,8 @@ _SIGS = {
     "sf_lammps_nbr_launches": (C.c_int, [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "sf_lammps_nbr_cost": (C.c_int, [vp, C.c_char_p, dp, dp]),
     "sf_lammps_cluster_rounds": (C.c_int, [vp, C.c_char_p, C.POINTER(C.c_int)]),
+    "sf_lammps_chunk_cost": (C.c_int, [vp, C.c_char_p, dp]),
+    "sf_lammps_chunk_info": (C.c_longlong, [vp, C.c_char_p, C.c_longlong, ip, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "sf_lammps_get_image": (C.c_int, [vp, ip]),
     "sf_lammps_region_match": (C.c_int, [vp, C.c_char_p, C.c_int, dp, ip]),
     "sf_lammps_group_mask": (C.c_int, [vp, C.c_char_p, ip]),

@@ -2,6 +2,8 @@
 // value ...` (sf_chunk.hip): atoms assigned to spatial bins and per-bin sums reduced on the GPU, averaged over time and
 // written as profiles.  The compute is a per-atom compute (one column, the chunk ID): compute_command (sf_compute_ids.hip) hands it
 // over through sf_compute_atom.hip, whose kind forwards here, so `c_ID` in dump custom and sf_lammps_compute_atom see it unchanged.
+// `compute ID group chunk/atom c_CID ...`, a chunk ID read from a per-atom compute, is held by sf_pchunk.hip: the functions of
+// the compute below forward to it what they do not hold.
 #pragma once
 #include <string>
 #include <vector>

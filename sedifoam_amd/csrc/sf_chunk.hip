@@ -34,6 +34,8 @@
 #include "sf_chunk_parse.h"
 #include "sf_compute_atom.h"
 #include "sf_compute_ids.h"
+#include "sf_pchunk.h"
+#include "sf_pchunk_parse.h"
 
 namespace sf {
 namespace {
@@ -492,6 +494,10 @@ const AveFixKind& ave_chunk_kind()
 
 void chunk_compute_define(SfLammps& L, const std::vector<std::string>& w)
 {
+  if (chunk_style_is_compute(w)) {   // (c_CID: the chunk ID is a compute's column; sf_pchunk.hip holds it, the functions below forward)
+    pchunk_atom_define(L, w);
+    return;
+  }
   refuse_decomposed(L, "compute chunk/atom");
   auto c = std::make_unique<ChunkCompute>();
   c->id = w[1];
@@ -509,7 +515,7 @@ void chunk_compute_define(SfLammps& L, const std::vector<std::string>& w)
 bool chunk_compute_shape(const SfLammps& L, const std::string& id, ComputeShape* s)
 {
   ChunkSet* T = set_of(L);
-  if (!T || !T->find(id)) return false;
+  if (!T || !T->find(id)) return pchunk_atom_shape(L, id, s);
   *s = ComputeShape();
   s->kind = CK_PERATOM;
   s->n = 1;
@@ -520,12 +526,15 @@ bool chunk_compute_shape(const SfLammps& L, const std::string& id, ComputeShape*
 void chunk_compute_remove(SfLammps& L, const std::string& id)
 {
   if (ChunkSet* T = set_of(L)) compute_take(L, T->computes, id);   // (a frame queued on the stream may still read its buffer)
+  pchunk_atom_remove(L, id);
 }
 
 const double* chunk_compute_values(SfLammps& L, const std::string& id)
 {
   ChunkSet* T = set_of(L);
   ChunkCompute* c = T ? T->find(id) : nullptr;
+  if (!c)
+    if (const double* val = pchunk_atom_values(L, id)) return val;
   if (!c) fail("Could not find compute ID %s", id.c_str());
   if (!c->assigned.is_now(L.eng)) assign(L, *T, *c);
   else refuse_decomposed(L, "compute chunk/atom");
@@ -557,6 +566,9 @@ void ave_chunk_fix_command(SfLammps& L, const std::string& line)
     fail("fix ave/chunk %s: this fix ID is in use (unfix it first)", F->S.id.c_str());
   fail_if(check_ave_chunk_id(compute_shape(L, F->S.chunk)));
   ChunkCompute* c = T.find(F->S.chunk);
+  if (!c)
+    fail("fix ave/chunk: chunk/atom compute %s takes its chunk IDs from a compute (c_ID), which is not supported (the output "
+         "needs layer coordinates and a fixed Nchunk; the per-chunk computes reduce over such chunks)", F->S.chunk.c_str());
   for (const AveValue& v : F->S.values)
     if (v.source == AS_COMPUTE) check_compute_value(L, v);
   F->nchunk = c->B.nchunk;

@@ -1,6 +1,6 @@
 // sf_compute_ids.h -- the one ID space of the computes: compute pair/local (sf_contacts.hip), the per-atom computes
-// (sf_compute_atom.hip, which forwards chunk/atom to sf_chunk.hip), the global computes (sf_global.hip) and compute rdf
-// (sf_nbr.hip).  The registry is sf_compute_ids.hip: it owns `compute` / `uncompute`, answers what an ID is, and tells every
+// (sf_compute_atom.hip, which forwards chunk/atom to sf_chunk.hip), the global computes (sf_global.hip), compute rdf
+// (sf_nbr.hip) and the per-chunk computes (sf_pchunk.hip).  The registry is sf_compute_ids.hip: it owns `compute` / `uncompute`, answers what an ID is, and tells every
 // owner that the state changed.  A kind plugs in with one ComputeKindOps.  What a reader of c_ID then accepts: sf_compute_ref.h.
 #pragma once
 #include <memory>
@@ -33,6 +33,7 @@ const ComputeKindOps& pair_local_kind();       // (sf_contacts.hip)
 const ComputeKindOps& atom_compute_kind();     // (sf_compute_atom.hip)
 const ComputeKindOps& global_compute_kind();   // (sf_global.hip)
 const ComputeKindOps& rdf_compute_kind();      // (sf_nbr.hip)
+const ComputeKindOps& pchunk_compute_kind();   // (sf_pchunk.hip: property/chunk, com/chunk, vcm/chunk, gyration/chunk)
 
 // compute `id` taken out of an owner's list once nothing queued on the stream can still read or write its buffers;
 // nullptr: no such compute

@@ -7,13 +7,14 @@
 #include "sf_chunk.h"
 #include "sf_contacts.h"
 #include "sf_global.h"
+#include "sf_pchunk.h"
 #include "sf_thermo.h"
 
 namespace sf {
 namespace {
-std::array<const ComputeKindOps*, 4> kinds()
+std::array<const ComputeKindOps*, 5> kinds()
 {
-  return {{&pair_local_kind(), &atom_compute_kind(), &global_compute_kind(), &rdf_compute_kind()}};
+  return {{&pair_local_kind(), &atom_compute_kind(), &global_compute_kind(), &rdf_compute_kind(), &pchunk_compute_kind()}};
 }
 
 // the kind that holds compute `id` and the compute's shape; nullptr: no compute has this ID
@@ -50,6 +51,8 @@ bool compute_command(SfLammps& L, const std::vector<std::string>& w)
     const ComputeKind kind = shape.kind;
     if (!owner) fail("Could not find compute ID to delete");   // [3P] Modify::delete_compute
     if (reduce_uses_compute(L, id)) fail("uncompute %s: a compute reduce still uses this compute (uncompute it first)", id.c_str());
+    if (const char* who = pchunk_uses_compute(L, id))
+      fail("uncompute %s: a %s still uses this compute (uncompute it first)", id.c_str(), who);
     if (const char* who = ave_fix_uses_compute(L, id))
       fail("uncompute %s: a %s still uses this compute (unfix it first)", id.c_str(), who);
     if (kind == CK_GLOBAL && thermo_uses_compute(L, id))
@@ -73,7 +76,8 @@ bool compute_command(SfLammps& L, const std::vector<std::string>& w)
          "computes stress/atom, contact/atom, ke/atom, erotate/sphere/atom, property/atom and chunk/atom, and the global "
          "computes reduce, ke and erotate/sphere; on unwrapped coordinates the per-atom compute displace/atom and the global "
          "compute com; on a grid of the user's cutoff the global array rdf and the per-atom computes coord/atom and cluster/atom, and "
-         "the global compute cluster/stats)", style.c_str());
+         "the global compute cluster/stats; over the chunks of a compute chunk/atom c_ID the global arrays property/chunk, "
+         "com/chunk, vcm/chunk and gyration/chunk)", style.c_str());
   (void)L.eng.group_bit(w[2]);   // (the group must exist, before the ID is looked at)
   if (compute_shape(L, w[1]).kind != CK_NONE) fail("Reuse of compute ID");
   owner->define(L, w);

@@ -15,7 +15,9 @@ struct ComputeShape {
   int n = 0;             // values of a local row, columns of a per-atom compute, length of a global compute, columns of an array
   bool vector = false;   // a global compute: read as c_ID[k]
   int rows = 0;          // an array
-  bool chunk = false;    // a per-atom compute: a chunk/atom one (sf_chunk.hip)
+  bool chunk = false;    // a per-atom compute: a chunk/atom one (sf_chunk.hip, sf_pchunk.hip)
+  bool rows_vary = false;   // an array: `rows` is that of the last evaluation and may change with the next (a per-chunk compute
+                            // whose chunk/atom compute has compress yes or nchunk every; sf_pchunk.hip)
 };
 
 // ---- dump custom: c_ID names a per-atom vector, c_ID[k] a column of a per-atom array ([3P] DumpCustom::parse_fields) ----
@@ -102,6 +104,9 @@ inline std::string check_ave_time_vector(const ComputeShape& s, long index, int 
   if (s.kind == CK_NONE) return "Compute ID for fix ave/time does not exist";
   if (s.kind != CK_ARRAY) return "Fix ave/time compute does not calculate an array";
   if (index > s.n) return "Fix ave/time compute array is accessed out-of-range";
+  if (s.rows_vary)
+    return "Fix ave/time compute array has a varying number of rows (mode vector takes a per-chunk compute only when its "
+           "chunk/atom compute is compress no nchunk once)";
   if (nrows > 0 && s.rows != nrows) return "Fix ave/time columns must all be the same length";
   return std::string();
 }

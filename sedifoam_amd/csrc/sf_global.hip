@@ -56,6 +56,7 @@
 #include "sf_displace.h"
 #include "sf_displace_parse.h"
 #include "sf_gather_col.h"
+#include "sf_pchunk.h"
 #include "sf_global.h"
 #include "sf_global_parse.h"
 #include "sf_nbr.h"
@@ -700,8 +701,9 @@ void check_fix_value(const SfLammps& L, const AveTimeValue& v)
 
 // mode vector: c_ID[k] is column k of a global array; every value of a fix has the same number of rows, which is returned.
 // Checked at the fix line and again at every sample
-int check_fix_column(const SfLammps& L, const AveTimeValue& v, int nrows, int* ncols = nullptr)
+int check_fix_column(SfLammps& L, const AveTimeValue& v, int nrows, int* ncols = nullptr)
 {
+  pchunk_prepare(L, v.id);   // (a per-chunk compute knows its rows once its chunk/atom compute is evaluated)
   const ComputeShape shape = compute_shape(L, v.id);
   fail_if(check_ave_time_vector(shape, v.index, nrows));
   if (ncols) *ncols = shape.n;
@@ -981,7 +983,7 @@ void global_step_due(SfLammps& L, const std::vector<std::string>& also)
         const AveTimeValue& v = f->S.values[j];
         int ncols = 0;
         check_fix_column(L, v, f->nrows, &ncols);
-        const double* src = rdf_array_device(L, v.id);
+        const double* src = pchunk_holds(L, v.id) ? pchunk_array_device(L, v.id, nullptr, nullptr) : rdf_array_device(L, v.id);
         k_global_col_acc<<<div_up(f->nrows, kGBlock), kGBlock, 0, L.eng.stream()>>>(src + (v.index - 1), ncols, f->nrows,
                                                                                     f->vacc + j, nv);
         SF_HIP(hipGetLastError());

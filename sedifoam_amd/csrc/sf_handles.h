@@ -101,6 +101,9 @@ struct SfLammps {
   // the compute rdf commands, the cutoff grids and their device buffers (sf_nbr.hip): goes after the fixes ave/time, whose
   // samples read its arrays
   OpaqueSlot nbr;
+  // the chunk/atom computes over c_ID and the per-chunk computes (sf_pchunk.hip): after the fixes ave/time, whose samples read
+  // their arrays, and after the dumps, whose frames read the chunk IDs
+  OpaqueSlot pchunks;
   // the per-atom computes and their device buffers (sf_compute_atom.hip): goes after the dumps, whose frames read them
   OpaqueSlot atom_computes;
   // the `compute pair/local` commands and the device scratch of their rows (sf_contacts.hip): after the dumps, likewise

@@ -45,6 +45,7 @@
 #include "sf_compute_atom.h"
 #include "sf_compute_ids.h"
 #include "sf_nbr.h"
+#include "sf_pchunk.h"
 #include "sf_unmap.h"
 
 // (a*a + s stays a product and a sum: rsq has the same bits from both sides of a pair and in the NumPy statement)
@@ -810,6 +811,19 @@ long long sf_lammps_compute_array(void* ptr, const char* id, long long max, doub
   SF_API_BEGIN
   sf::SfLammps& L = *handle(ptr);
   if (!id) sf::fail("sf_lammps_compute_array: null argument");
+  if (sf::pchunk_holds(L, id)) {   // (a per-chunk compute: Nchunk rows, known once its chunk/atom compute is evaluated)
+    int rows = 0, nc = 0;
+    const double* d = sf::pchunk_array_device(L, id, &rows, &nc);
+    if (ncols) *ncols = nc;
+    n = (long long)rows * nc;
+    if (n > 0 && n <= max) {
+      if (!values) sf::fail("sf_lammps_compute_array: null argument");
+      hipStream_t st = L.eng.stream();
+      SF_HIP(hipMemcpyAsync(values, d, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+      SF_HIP(hipStreamSynchronize(st));
+    }
+    return n;
+  }
   const sf::ComputeShape shape = sf::compute_shape(L, id);
   sf::fail_if(sf::check_get_array(shape, id));
   if (ncols) *ncols = shape.n;

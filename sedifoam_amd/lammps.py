@@ -255,7 +255,9 @@ class Lammps:
     def compute_array(self, cid):
         """the global array of `compute cid group rdf Nbin [itype jtype ...] cutoff Rc` on the positions as they stand:
         float64 [Nbin, 1 + 2 npairs] -- the bin centre, then g(r) and the running coordination number of each pair.  What a
-        fix ave/time mode vector sample taken at this moment holds.  Passive: the run goes on with the same bits"""
+        fix ave/time mode vector sample taken at this moment holds.  A per-chunk compute (property/chunk, com/chunk, vcm/chunk,
+        gyration/chunk) gives float64 [Nchunk, ncol], row m - 1 chunk m: [Nchunk, 1] for one column, (0, ncol) without chunks.
+        Passive: the run goes on with the same bits"""
         cid = str(cid).encode()
         nc = C.c_int()
         n = check(self.L.sf_lammps_compute_array(self.ptr, cid, 0, None, C.byref(nc)))
@@ -299,6 +301,26 @@ class Lammps:
         r = C.c_int()
         check(self.L.sf_lammps_cluster_rounds(self.ptr, str(cid).encode(), C.byref(r)))
         return r.value
+
+    def chunk_info(self, cid):
+        """dict(nchunk, ids, launches, host_copies) of `compute cid group chunk/atom c_ID ...` on the state as it stands: ids
+        int32 [nchunk], the original IDs under compress yes and 1 .. nchunk otherwise; launches and host_copies: the kernel
+        launches and the device-to-host copies (4 bytes each: Nchunk) that the evaluations of this compute and of the per-chunk
+        computes over it have made so far"""
+        cid = str(cid).encode()
+        la = C.c_longlong(); hc = C.c_longlong()
+        n = check(self.L.sf_lammps_chunk_info(self.ptr, cid, 0, None, C.byref(la), C.byref(hc)))
+        ids = np.zeros(n, np.int32)
+        m = check(self.L.sf_lammps_chunk_info(self.ptr, cid, n, ids.ctypes.data_as(C.POINTER(C.c_int)), C.byref(la), C.byref(hc)))
+        assert m == n
+        return dict(nchunk=int(n), ids=ids, launches=la.value, host_copies=hc.value)
+
+    def chunk_cost(self, cid):
+        """GPU ms of one evaluation now of chunk/atom compute `cid` (over c_ID) and of every per-chunk compute over it; the
+        compute behind c_ID is evaluated before the clock starts"""
+        ms = C.c_double()
+        check(self.L.sf_lammps_chunk_cost(self.ptr, str(cid).encode(), C.byref(ms)))
+        return ms.value
 
     def global_launches(self):
         """dict(launches, host_copies): kernel launches made for global computes and fix ave/time so far, and the
