@@ -295,6 +295,10 @@ typedef struct {
   long long npairs_full; /* sum of numneigh over owned atoms (full list) */
 } sf_dem_info;
 int sf_dem_get_info(void *ptr, sf_dem_info *out);
+/* debug statistic of the current neighbour list, waves of 64 consecutive owned atoms: of the (atom, slot) pairs with a next
+ * lane and a next slot, the fraction whose next slot names the root atom that the next lane's slot names -- the records
+ * the sub-step kernel takes from the next lane's registers (SF_LANE_REUSE).  Runs a kernel and synchronises. */
+int sf_dem_lane_reuse_fraction(void *ptr, double *fraction);
 /* device pointers into the engine's state (valid until the next rebuild / step):
  *   xr, vm, om : double4 records (x,y,z,radius) (vx,vy,vz,rmass) (wx,wy,wz,0)
  *   fdrag      : component-major [3][capacity] doubles ; tag/type : int32 [capacity] */

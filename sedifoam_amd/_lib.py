@@ -162,6 +162,7 @@ _SIGS = {
     "sf_dem_create_atoms": (C.c_int, [vp, C.c_int, dp, dp, dp, dp, dp, ip, ip]),
     "sf_dem_set_box": (C.c_int, [vp, dp, dp]),
     "sf_dem_get_info": (C.c_int, [vp, C.POINTER(DemInfo)]),
+    "sf_dem_lane_reuse_fraction": (C.c_int, [vp, dp]),
     "sf_dem_device_view_get": (C.c_int, [vp, C.POINTER(DemDeviceView)]),
     "sf_dem_set_profiling": (C.c_int, [vp, C.c_int]),
     "sf_dem_get_profile": (C.c_int, [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),

@@ -618,6 +618,9 @@ class DemEngine {
   }
 
   long long nbuilds() const { return nbuilds_; }
+  // of the (atom, slot) pairs of the current list that have a next lane and a next slot: the fraction whose next slot
+  // names the root the next lane's slot names (k_lane_reuse_stat; synchronises)
+  double lane_reuse_fraction(bool adopting = false);   // (adopting: called while the new list is being adopted)
   long long nsteps() const { return nsteps_; }
   int max_neigh_used() const { return max_neigh_used_; }
   int max_neigh_cap() const { return M_; }
@@ -874,6 +877,7 @@ private:
   bool in_run_ = false;                      // rebuild() called from the stepping loop of run()
   RebuildPredictor predict_;                 // single-domain run(): how far to queue (SF_QUEUE_PREDICT=0: everything)
   int nt_policy_ = 2, nt_policy_env_ = -1;   // non-temporal policy of the row streams (sf_dem_kernels.h, NTP)
+  bool lane_reuse_ = true;                   // neighbour records from the next lane's registers (SF_LANE_REUSE, sf_lane_reuse_variant)
   void measure_list();     // queue k_partner_coalescing on the current list (results with the next flag read)
   ListStats list_stats() const;   // the four counters of the last measurement, as the flag words hold them on the host
   long long list_sampled_ = 0;   // atoms the last measure_list looked at

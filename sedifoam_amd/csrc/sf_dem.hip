@@ -139,6 +139,7 @@ DemEngine::DemEngine()
   touch_prefetch_env_ = env_int("SF_TOUCH_PREFETCH", touch_prefetch_env_);
   touch_first_env_ = env_int("SF_TOUCH_FIRST", touch_first_env_);
   nt_policy_env_ = env_int("SF_NT_POLICY", nt_policy_env_);
+  lane_reuse_ = env_flag("SF_LANE_REUSE", lane_reuse_);
   opt_lpa_ = env_int("SF_LPA", opt_lpa_);
   opt_ghost_free_ = env_int("SF_GHOST_FREE", opt_ghost_free_);
   predict_.on = env_flag("SF_QUEUE_PREDICT", predict_.on);
@@ -900,16 +901,27 @@ StepParams DemEngine::step_params(int mode, int kstep) const
 // The plain kernel's remaining axes, below pair_dispatch (sf_dem_dispatch.h): lanes per atom, TP (v, omega of the touching
 // neighbours prefetched: touch_prefetch_), ntp (non-temporal policy of the row streams, sf_dem_kernels.h) and GS
 template <int STYLE, bool COHE, bool LUB, bool GS>
-static void launch_plain(int lpa, bool tp, int ntp, dim3 grid, int block, hipStream_t s, const DemPtrs& P,
+static void launch_plain(int lpa, bool tp, int ntp, bool reuse, dim3 grid, int block, hipStream_t s, const DemPtrs& P,
                          const StepParams& S)
 {
-  auto go = [&](auto lanes, auto policy) {
+  // (lane reuse: a second instantiation only of the Hertz kernels sf_lane_reuse_variant names)
+  auto one = [&](auto lanes, auto policy, auto touch) {
     constexpr int LPA = decltype(lanes)::value, NTP = decltype(policy)::value;
+    constexpr bool TP = decltype(touch)::value;
+    if constexpr (STYLE == 2 && sf_lane_reuse_variant(COHE, LUB, LPA, TP, NTP, GS, false)) {   // (substep_particle: LANE_REUSE)
+      if (reuse) {
+        k_substep<STYLE, COHE, LUB, LPA, TP, NTP, GS, false, true><<<grid, block, 0, s>>>(P, S);
+        return;
+      }
+    }
+    k_substep<STYLE, COHE, LUB, LPA, TP, NTP, GS><<<grid, block, 0, s>>>(P, S);
+  };
+  auto go = [&](auto lanes, auto policy) {
     // lubrication needs v, omega of every neighbour anyway: TP = true, one instantiation (with cohesion as well the
     // TP = false one is compiled too, and never launched)
-    if constexpr (LUB && !COHE) k_substep<STYLE, COHE, LUB, LPA, true, NTP, GS><<<grid, block, 0, s>>>(P, S);
-    else if (tp || LUB) k_substep<STYLE, COHE, LUB, LPA, true, NTP, GS><<<grid, block, 0, s>>>(P, S);
-    else k_substep<STYLE, COHE, LUB, LPA, false, NTP, GS><<<grid, block, 0, s>>>(P, S);
+    if constexpr (LUB && !COHE) one(lanes, policy, std::true_type{});
+    else if (tp || LUB) one(lanes, policy, std::true_type{});
+    else one(lanes, policy, std::false_type{});
   };
   // systems small enough for several lanes per atom always fit the memory-side cache (policy 0); ghost slots (sf_halo_rccl.hip)
   // are the per-GPU share of a decomposed bed, nothing non-temporal: one variant per lane count
@@ -1119,7 +1131,7 @@ void DemEngine::substep_dispatch(dim3 grid, int block, int lpa, const DemPtrs& P
   pair_dispatch(gran_.style, cohe_.enabled, lub_.enabled, [&](auto style, auto cohe, auto lub) {
     if (lds_active_) launch_lds_one<style, cohe, lub>(grid, (size_t)stage_cap_ * 88, stream_, P, S);
     else flag_dispatch(S.gs_on != 0, [&](auto gs) {
-      launch_plain<style, cohe, lub, gs>(lpa, touch_prefetch_, nt_policy_, grid, block, stream_, P, S);
+      launch_plain<style, cohe, lub, gs>(lpa, touch_prefetch_, nt_policy_, lane_reuse_, grid, block, stream_, P, S);
     });
   });
 }
@@ -1920,6 +1932,8 @@ void DemEngine::measure_list()
               "(x 2 halves = %.1f accesses per record gather); lane pairs sharing a record: %.1f + %.1f = %.1f; 64-B half "
               "lines %.1f\n", h[0], (double)h[1] / h[0], (double)h[2] / h[0], 2.0 * h[2] / h[0], (double)h[3] / h[0],
               (double)h[4] / h[0], (double)(h[3] + h[4]) / h[0], (double)h[5] / h[0]);
+    fprintf(stderr, "[sedifoam_amd] lane reuse: %.3f of the (atom, slot) pairs with a next lane and a next slot find the next "
+            "slot's root in the next lane\n", lane_reuse_fraction(true));
   }
   static_assert(F_PART_COAL == F_PART_SLOTS + 1 && F_LIST_SLOTS == F_PART_SLOTS + 2 && F_LIST_TOUCH == F_PART_SLOTS + 3,
                 "adjacent counters");
@@ -1931,6 +1945,21 @@ void DemEngine::measure_list()
   for (int b = 0; b < nsamp; b++) list_sampled_ += std::min(1024, nlocal_ - b * stride * 1024);
   k_partner_coalescing<<<nsamp, 1024, 0, stream_>>>(neigh_.as<int>(), numneigh_.as<int>(), nlocal_, cap_,
                                                     d_flags_ + F_PART_SLOTS, stride);
+}
+
+// Debug statistic of the lane reuse of the sub-step kernel (sf_dem_kernels.h, lane_up), over the whole current list
+double DemEngine::lane_reuse_fraction(bool adopting)
+{
+  if (!nlocal_ || !roots_ || !(have_list_ || adopting)) return 0.0;
+  unsigned long long* d = nullptr;
+  unsigned long long h[2] = {0, 0};
+  SF_HIP(hipMalloc(&d, sizeof h));
+  SF_HIP(hipMemsetAsync(d, 0, sizeof h, stream_));
+  k_lane_reuse_stat<<<div_up(nlocal_, 64), 64, 0, stream_>>>(neigh_.as<int>(), numneigh_.as<int>(), nlocal_, cap_, d);
+  SF_HIP(hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, stream_));
+  SF_HIP(hipStreamSynchronize(stream_));
+  SF_HIP(hipFree(d));
+  return h[0] ? (double)h[1] / (double)h[0] : 0.0;
 }
 
 void DemEngine::choose_kernel()

@@ -13,7 +13,8 @@
 
 // Instrumentation of variant builds (tests/build_variant.sh): SF_EXP_STAMP / SF_EXP_PHASE, the workgroup timeline of one
 // launch -- sf_dem_variants.h.  The pricing arms of rounds 1-4 (history traffic off, agent-coherent access forms, LDS-DMA
-// row streams, the no-wait persistent kernel, neighbour records by lane shuffle, the two-lane launch tail) were measured,
+// row streams, the no-wait persistent kernel, neighbour records by a per-lane shuffle in every slot -- lane_up below is its
+// successor --, the two-lane launch tail) were measured,
 // written up (docs/history_r01_r03.md, profiles/r04_README.md, profiles/r05_README.md) and removed from this file.  So were
 // those of rounds 5 and 6 (profiles/r05_README.md, profiles/r06_README.md): the persistent-tile kernel,
 // the ghost-slot hand-off with one part compiled out, the reversed sweep, and the compile-time switches of the neighbour
@@ -120,20 +121,80 @@ __device__ __forceinline__ void coop_indices(const int j, const bool vw, int& ja
   vwa = (int)a < 0;
   vwb = (int)b < 0;
 }
+// ... and whether the lane takes the record from its next lane's registers (lane reuse): bit 30
+__device__ __forceinline__ void coop_indices(const int j, const bool vw, const bool reuse, int& ja, int& jb, bool& vwa,
+                                             bool& vwb, bool& ra, bool& rb)
+{
+  unsigned a = (unsigned)j | (vw ? 0x80000000u : 0u) | (reuse ? 0x40000000u : 0u), b = a;
+  swap32(a, b);
+  ja = (int)(a & (unsigned)kIdxMask);
+  jb = (int)(b & (unsigned)kIdxMask);
+  vwa = (int)a < 0;
+  vwb = (int)b < 0;
+  ra = (a & 0x40000000u) != 0;
+  rb = (b & 0x40000000u) != 0;
+}
 // (half: byte offset of the lane's half of a record -- 0 in lanes 0..31, 16 in lanes 32..63)
+// (pre: what a record that is not loaded holds instead -- zeros, or the next lane's record, see lane_up)
 __device__ __forceinline__ double4 coop_load(const double4* arr, const int ja, const int jb, const int half,
-                                             const bool wa = true, const bool wb = true)
+                                             const bool wa = true, const bool wb = true,
+                                             const double4 pre = double4{0.0, 0.0, 0.0, 0.0})
 {
   const char* p = reinterpret_cast<const char*>(arr);
-  double2 a = {0.0, 0.0}, b = {0.0, 0.0};
+  double2 a = {pre.x, pre.y}, b = {pre.z, pre.w};
   if (wa) a = *reinterpret_cast<const double2*>(p + (((unsigned)ja << 5) | (unsigned)half));
   if (wb) b = *reinterpret_cast<const double2*>(p + (((unsigned)jb << 5) | (unsigned)half));
   return double4{a.x, a.y, b.x, b.y};
 }
 
+// ------------------------------------------------------------------------------------------------
+// Lane reuse.  Atoms are sorted by half-cutoff cells, x fastest, and the list is in candidate order: the two neighbours an
+// atom has in an adjacent row of the packing are consecutive atoms j, j + 1 in consecutive slots s, s + 1, and the next
+// atom of the sort -- the next lane -- has j + 1, j + 2 there.  The record lane l wants for slot s + 1 is then the one lane
+// l + 1 holds for slot s: it is taken from that lane's registers (one whole-wave shift by one lane per dword) instead of
+// being gathered again.  Same records into the same arithmetic: the same bits.
+// lane_up(old, v): lane l receives v of lane l + 1; lane 63, and a lane whose source lane is not active, receive `old`.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int lane_up(const int old, const int v)
+{
+  return __builtin_amdgcn_update_dpp(old, v, 0x130 /* wave_shl:1 */, 0xf, 0xf, false);
+}
+// (records: the lanes without a source receive 0 -- they do not reuse, the value is not looked at -- so that the move needs
+// no previous value of its destination)
+__device__ __forceinline__ double lane_up(const double v)
+{
+  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0x130, 0xf, 0xf, true);
+  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0x130, 0xf, 0xf, true);
+  return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double4 lane_up(const double4& r)
+{
+  return double4{lane_up(r.x), lane_up(r.y), lane_up(r.z), lane_up(r.w)};
+}
+// a record nobody looks at: registers without a value, and without an instruction that would give them one (K: one
+// statement per record -- equal statements would be merged into one record and copied)
+template <int K>
+__device__ __forceinline__ double4 unset_record()
+{
+  double4 r;
+  asm("" : "=v"(r.x), "=v"(r.y), "=v"(r.z), "=v"(r.w) : "i"(K));
+  return r;
+}
+// Which kernels take the path -- measured (profiles/lane_reuse_README.md): the plain contact kernel that gathers by half
+// waves (one lane per atom, a bed beyond the memory-side cache, every lane of the wave in the loop with v, omega of its
+// neighbour): the 1 M headline bed -6.1 %, 2 M -6.0 %.  The kernel with both the cohesive and the lubrication arm is
+// neutral on the 500 k polydisperse bed (+0.9 / -0.4 %, inside its own spread) and stays as it was; the plain-gather
+// kernels and the ones that ask for v, omega by touch bit (loose beds: 0.04 of their pairs match) have not been
+// measured with it and do not take it.  No ghost slots, no rigid bodies.
+__host__ __device__ constexpr bool sf_lane_reuse_variant(bool cohe, bool lub, int lpa, bool tp, int ntp, bool gs, bool rigid)
+{
+  return !cohe && !lub && !gs && !rigid && sf_coop_variant(cohe, lub, lpa, tp, ntp);
+}
+
 // RIGID (fix rigid/nve, sf_rigid.h): the pair law sees the mass of an atom's body on both sides (DemPtrs::mbody), force and
 // torque are stored and nothing is integrated -- the bodies and the free atoms are advanced by the kernels of sf_rigid.hip.
-template <int STYLE, bool COHE, bool LUB, bool LDS, int LPA, bool TP, int NTP, bool GS = false, bool RIGID = false>
+template <int STYLE, bool COHE, bool LUB, bool LDS, int LPA, bool TP, int NTP, bool GS = false, bool RIGID = false,
+          bool REUSE = false>
 __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepParams& S, const int i, const int q,
                                                  const double4* lx, const double4* lv, const double* lw,
                                                  const unsigned long long gs_w = 0ull, const bool live = true)
@@ -142,6 +203,10 @@ __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepPara
   // to the wave's largest count, `live` = this lane holds an atom (the caller clamps i of the others to a valid one: they
   // load, take part in the exchanges, and store nothing)
   constexpr bool COOP = !LDS && sf_coop_variant(COHE, LUB, LPA, TP, NTP);
+  // REUSE: a neighbour's records are taken from the next lane's registers where it holds them (lane_up)
+  // (the Hertz law only: the Hookean instantiation, which spills 28 bytes as it is, spills 44 with the path -- not taken,
+  // not measured; nor is the kernel without a contact law)
+  constexpr bool LANE_REUSE = REUSE && !LDS && STYLE == 2 && sf_lane_reuse_variant(COHE, LUB, LPA, TP, NTP, GS, RIGID);
   const int coop_half = (int)(threadIdx.x & 32) >> 1;   // (byte offset of this lane's half of a record: 0 | 16)
   const size_t cap = (size_t)S.cap;
   const bool shearupdate = (S.mode != 2);
@@ -223,14 +288,43 @@ __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepPara
     return NEED_VW && (LUB || !TP || (jraw & kTouchBit) != 0);
   };
   // request the records of the neighbour in `slot` (global gather), or its LDS position
-  auto fetch = [&](int jraw, int slotrow, Rec& R) {
+  // (from: the complete records of the slot before, or null -- lane reuse, see lane_up)
+  auto fetch = [&](int jraw, int slotrow, Rec& R, const Rec* from) {
     if (LDS) {
       R.l = (P.nloc + (size_t)slotrow * cap)[i];
     } else {
       const int j = neigh_index(jraw, ROOTS);
-      R.l = j;   // (gather mode: the root index, used by the register reuse below)
+      R.l = j;   // (gather mode: the root index, compared by the next slot's lane reuse)
       R.vw = wants_vw(jraw);
-      if (COOP) {   // (every lane of the wave is here; merged by the consumer, coop_merge)
+      // Lane reuse: the next lane holds the root this lane wants next (x, v, omega are the unshifted root records, the
+      // image is applied where they are consumed; every lane of these kernels holds v, omega of its neighbour, and a lane
+      // beyond its count sits on word 0 with atom 0's records).  The records of `from` are shifted into R in ALL lanes
+      // BEFORE any load into R is issued -- a register move into R behind its loads would wait for them -- and only the
+      // other lanes load.  No lane reuses (one compare, one ballot): nothing is moved, every lane loads.
+      if (LANE_REUSE && from) {
+        static_assert(!LANE_REUSE || (COOP && !TP), "lane reuse: the half-wave gather, v and omega in every lane");
+        const bool reuse = lane_up(-1, from->l) == j;
+        // (one code path for the loads of both cases: the slot in which no lane reuses predicates them on nothing)
+        double4 px, pv, pw;
+        if (__ballot(reuse)) {
+          // (coop_merge is its own inverse: what coop_finish turns back into the next lane's record)
+          px = coop_merge(lane_up(from->x));
+          pv = coop_merge(lane_up(from->v));
+          pw = coop_merge(lane_up(from->w));
+        } else {
+          px = unset_record<0>();
+          pv = unset_record<1>();
+          pw = unset_record<2>();
+        }
+        int ja, jb;
+        bool vwa, vwb, ra, rb;
+        coop_indices(j, R.vw, reuse, ja, jb, vwa, vwb, ra, rb);
+        R.x = coop_load(P.xr_in, ja, jb, coop_half, !ra, !rb, px);
+        if (NEED_VW) {
+          R.v = coop_load(P.vm_in, ja, jb, coop_half, !ra && vwa, !rb && vwb, pv);
+          R.w = coop_load(P.om_in, ja, jb, coop_half, !ra && vwa, !rb && vwb, pw);
+        }
+      } else if (COOP) {   // (every lane of the wave is here; merged by the consumer, coop_merge)
         int ja, jb;
         bool vwa, vwb;
         coop_indices(j, R.vw, ja, jb, vwa, vwb);
@@ -306,7 +400,7 @@ __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepPara
     nn_wave = __builtin_amdgcn_readfirstlane(nn_wave);
   }
   if (COOP ? nn_wave > 0 : nn > 0) {
-    fetch(jraw_n1, q, RA);
+    fetch(jraw_n1, q, RA, nullptr);
     coop_finish(RA);
   }
 
@@ -328,7 +422,7 @@ __device__ __forceinline__ int substep_particle(const DemPtrs& P, const StepPara
     jraw_n1 = jraw_n2;
     if (s + 2 < nn) jraw_n2 = ld_stream<NT_LD>(&(nrow + (size_t)(2 * LPA) * cap)[i]);
     else if (COOP) jraw_n2 = 0;   // (a lane beyond its count keeps loading for its partner: word 0 = atom 0, no bits)
-    if (more) fetch(jraw_n1, sl + LPA, nxt);
+    if (more) fetch(jraw_n1, sl + LPA, nxt, &cur);
     double4 xj4 = cur.x, vj4 = cur.v, wj4 = cur.w;
     if (LDS) {
       xj4 = lx[cur.l];
@@ -670,7 +764,7 @@ __device__ __forceinline__ int xcd_contiguous_block()
 // TP: v and omega of a neighbour are requested with its x only when the pair touched one sub-step ago (a bed that
 // lists many more neighbours than it touches: -11 % in the loose disordered bed), or always (a bed whose listed
 // neighbours nearly all touch: the bookkeeping of the former costs 4 % there)
-template <int STYLE, bool COHE, bool LUB, int LPA, bool TP, int NTP, bool GS = false, bool RIGID = false>
+template <int STYLE, bool COHE, bool LUB, int LPA, bool TP, int NTP, bool GS = false, bool RIGID = false, bool REUSE = false>
 __global__ __launch_bounds__(256) SF_SUBSTEP_ATTR void k_substep(DemPtrs P, StepParams S)
 {
   // a previous sub-step of this batch moved an atom beyond skin/2: the list is stale, do nothing
@@ -746,7 +840,7 @@ __global__ __launch_bounds__(256) SF_SUBSTEP_ATTR void k_substep(DemPtrs P, Step
     if (__ballot(ran == 0)) return;   // (stopped at the gate -- the whole wave did: the gate is a wave-level decision)
     if (S.mode == 0) gs_done(P, S, (ran & 2) != 0, (ran & 4) != 0, gs_poller, gs_expected);
   } else {
-    substep_particle<STYLE, COHE, LUB, false, LPA, TP, NTP, false, RIGID>(P, S, i, q, nullptr, nullptr, nullptr, 0ull, live);
+    substep_particle<STYLE, COHE, LUB, false, LPA, TP, NTP, false, RIGID, REUSE>(P, S, i, q, nullptr, nullptr, nullptr, 0ull, live);
   }
   if (S.xcd_time && threadIdx.x == 0 && ((blockIdx.x >> 3) & 7) == 0)
     atomicMax(&P.xcd_time[xq + 32], (int)(wall_clock64() & 0x3fffffff));

@@ -199,6 +199,32 @@ __global__ __launch_bounds__(64) void k_gather_lines(const int* neigh, const int
   }
 }
 
+// Debug statistic of the lane reuse (sf_dem_kernels.h, lane_up): one wave = 64 consecutive atoms, one lane per atom.  Of the
+// (atom i, slot s) with a next lane (i % 64 != 63, i + 1 an atom) and a next slot (s + 1 < numneigh[i]): how many find the
+// root of their next word in the next lane's slot s.  out: {pairs looked at, pairs that match}
+__global__ __launch_bounds__(64) void k_lane_reuse_stat(const int* neigh, const int* numneigh, int nlocal, size_t cap,
+                                                        unsigned long long* out)
+{
+  const int lane = threadIdx.x;
+  const int i = blockIdx.x * 64 + lane;
+  unsigned long long pairs = 0, match = 0;
+  if (i < nlocal && lane != 63 && i + 1 < nlocal) {
+    const int nn = numneigh[i], nn_next = numneigh[i + 1];
+    for (int s = 0; s + 1 < nn; s++) {
+      pairs++;
+      if (s < nn_next && (neigh[(size_t)(s + 1) * cap + i] & kIdxMask) == (neigh[(size_t)s * cap + i + 1] & kIdxMask)) match++;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    pairs += __shfl_xor(pairs, off, 64);
+    match += __shfl_xor(match, off, 64);
+  }
+  if (lane == 0 && pairs) {
+    atomicAdd(&out[0], pairs);
+    atomicAdd(&out[1], match);
+  }
+}
+
 struct PbcParams {
   double lo[3], hi[3];
   int wrap[3];

@@ -1035,6 +1035,13 @@ int sf_dem_get_info(void* ptr, sf_dem_info* out)
   SF_API_END(0)
 }
 
+int sf_dem_lane_reuse_fraction(void* ptr, double* fraction)
+{
+  SF_API_BEGIN
+  *fraction = H(ptr)->eng.lane_reuse_fraction();
+  SF_API_END(0)
+}
+
 int sf_dem_device_view_get(void* ptr, sf_dem_device_view* out)
 {
   SF_API_BEGIN

@@ -455,6 +455,13 @@ class Lammps:
         check(self.L.sf_dem_get_info(self.ptr, C.byref(out)))
         return out
 
+    def lane_reuse_fraction(self):
+        """Of the (atom, slot) pairs of the current list with a next lane (waves of 64 consecutive atoms) and a next slot:
+        the fraction whose next slot names the root the next lane's slot names (what SF_LANE_REUSE serves from registers)."""
+        out = C.c_double()
+        check(self.L.sf_dem_lane_reuse_fraction(self.ptr, C.byref(out)))
+        return out.value
+
     def device_view(self):
         out = _lib.DemDeviceView()
         check(self.L.sf_dem_device_view_get(self.ptr, C.byref(out)))
